@@ -34,7 +34,20 @@ fognet_run_generated_dev: each 64-publish chunk of a trace is generated inside
 the replay kernel (the whole trace would be ~120 GB) and only statistics are
 kept (no trace and no per-task output in memory).
 
-  python bench.py [--gpus N --steps K --warmup W] [--workload c1|c3|c4|c5]
+A plain run sets up, warms up, times the steps and prints the result line
+(metric, value, ms_per_step, configuration, the HIP-event kernel time and the
+job statistics of the last step).  ``--full`` adds everything that takes work
+of its own: the CPU baseline and its parity check against the device, the
+reference-defined prefix (``reference_abort``, ``value_ref_defined``), the
+escalation census of EXT_HIER and the committed PMC / rocprofv3 figures quoted
+in ``roofline``; those keys are null in a plain line.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller
+as ``DIR/<name>.npy`` (float32 / float64; see dump_outputs): with the same
+arguments the inputs are the same in every run, so two builds can be compared
+array for array.
+
+  python bench.py [--gpus N --steps K --warmup W] [--workload c1|c3|c4|c5] [--full] [--dump-outputs DIR]
   torchrun --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -89,6 +102,57 @@ def log(msg: str):
     print(msg, file=sys.stderr, flush=True)
 
 
+DUMP_SEED = 0xD0C5EED
+DUMP_TASKS = 1 << 20  # per-task entries kept of a larger output (5 arrays, 36 MB)
+DUMP_REPS = 1 << 16   # replication records kept of a larger batch (27 arrays, 14 MB)
+
+
+def dump_sample(n: int, k: int):
+    """Sorted positions of the fixed, seeded sample of ``k`` out of ``n`` entries
+    (the same in every run); None when n <= k: everything is kept."""
+    if n <= k:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=k))
+
+
+def dump_outputs(dirname, rank, world, per_task=None, records=None, arrays=None):
+    """``--dump-outputs``: what the last timed step handed its caller, as
+    ``<name>.npy`` (``<name>.rank<r>.npy`` with several ranks), under 64 MB in all.
+    ``per_task``: {name: [R, T] device tensor}, written whole or, above DUMP_TASKS
+    entries, at the flat positions of ``task_index``; ``records``: {prefix: record
+    array}, one ``<prefix>_<field>`` array per field, of every replication or,
+    above DUMP_REPS, of the replications of ``<prefix>_index``; ``arrays``: small
+    arrays written whole.  Integers of up to 16 bits are written as float32, all
+    else as float64 (ticks and 64-bit limbs above 2^53 are rounded to it)."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f".rank{rank}" if world > 1 else ""
+
+    def save(name, a):
+        a = np.asarray(a)
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"),
+                np.ascontiguousarray(a, dtype=np.float32 if a.dtype.itemsize <= 2 else np.float64))
+
+    if per_task:
+        first = next(iter(per_task.values()))
+        idx = dump_sample(first.numel(), DUMP_TASKS)
+        if idx is not None:
+            save("task_index", idx)
+            sel = torch.from_numpy(idx).to(first.device)
+        for name, t in per_task.items():
+            save(name, (t if idx is None else t.reshape(-1)[sel]).cpu().numpy())
+    for prefix, rec in (records or {}).items():
+        rec = np.atleast_1d(rec)
+        idx = dump_sample(len(rec), DUMP_REPS)
+        if idx is not None:
+            save(f"{prefix}_index", idx)
+            rec = rec[idx]
+        for f in rec.dtype.names:
+            save(f"{prefix}_{f}", rec[f])
+    for name, a in (arrays or {}).items():
+        save(name, a)
+    log(f"[rank {rank}] outputs of the last timed step written to {dirname}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -118,6 +182,11 @@ def main():
     ap.add_argument("--block", type=int, default=0,
                     help="c4: replications per fognet_run_generated_dev call (0: the rank's whole shard in one "
                          "launch; its resident workgroups take replications from a work counter)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline and its parity check, the reference-defined prefix, the EXT_HIER "
+                         "escalation census and the committed PMC / rocprofv3 figures (null in a plain line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
     if args.policy is None:
         args.policy = "EXT_HIER" if args.workload == "c5" else "REF_V3"
@@ -239,6 +308,11 @@ def main():
     job = fa.merge_job_stats(list(jobs))
     summary = fa.summarize(job)
     hist = out.hist.cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world,
+                     per_task={"node": out.node, "status": out.status, "start_tick": out.start_tick,
+                               "done_tick": out.done_tick},
+                     records={"rep": rep, "job": jobs}, arrays={"hist": hist, "energy_j": energy.cpu().numpy()})
 
     decisions = (args.R_total if args.workload == "c5" else world * R) * T * args.steps
     value = decisions / elapsed
@@ -250,7 +324,7 @@ def main():
     default_policy = "EXT_HIER" if args.workload == "c5" else "REF_V3"
     prof = os.path.join(ROOT, "profiles", ("pmc_traffic" if args.workload == "c3" else f"pmc_traffic_{args.workload}")
                         + ("" if args.policy == default_policy else f"_{args.policy}") + ".json")
-    if os.path.exists(prof):
+    if args.full and os.path.exists(prof):
         try:
             pj = json.load(open(prof))
             if pj.get("config") == {"R": R, "T": T, "N": N, "ring": args.ring} and \
@@ -266,9 +340,12 @@ def main():
                             "source": os.path.relpath(prof, ROOT)}
         except Exception:
             traffic = None
-    ref = reference_prefix(rep, trace["arrive"])
+    ref = reference_prefix(rep, trace["arrive"]) if args.full else None
     hier_esc = None
-    if args.policy == "EXT_HIER" and N > _abi.HIER_REGION_NODES:
+    if not args.full and args.policy == "EXT_HIER" and N > _abi.HIER_REGION_NODES:
+        # a plain run: only the path each launch took (host-side counters), no census of the outputs
+        hier_esc = dict(zip(("region_launches", "sequential_launches"), ctx.hier_path_stats()))
+    elif args.policy == "EXT_HIER" and N > _abi.HIER_REGION_NODES:
         # escalations of the last step: a publish escalated iff its node lies outside its regional broker's
         # region; a replication with any is handed back by the region pass to the sequential wide kernel
         esc = (out.node // _abi.HIER_REGION_NODES) != trace["region"]
@@ -280,7 +357,7 @@ def main():
         # the path each launch took (fognet_hier_path_stats, warm-up included): the region pass, or
         # straight to the sequential replay once a region pass handed most replications over
         hier_esc["region_launches"], hier_esc["sequential_launches"] = ctx.hier_path_stats()
-    if dist is not None:  # job totals over the ranks' shards
+    if dist is not None and ref is not None:  # job totals over the ranks' shards
         tot = torch.tensor([ref["ref_defined_decisions"], ref["ref_aborted_replications"], ref["replications"]],
                            dtype=torch.int64, device=dev)
         dist.all_reduce(tot)
@@ -288,11 +365,13 @@ def main():
             (int(x) for x in tot.cpu().tolist())
     # the rate over the decisions the reference itself defines (the prefix up to each replication's abort
     # point): the same elapsed time, only the reference-defined decisions counted
-    value_ref = ref["ref_defined_decisions"] * args.steps / elapsed
-    ref["decisions_per_step"] = decisions // args.steps
+    value_ref = None
+    if ref is not None:
+        value_ref = ref["ref_defined_decisions"] * args.steps / elapsed
+        ref["decisions_per_step"] = decisions // args.steps
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(trace, args, R, T, N, out=out)
 
     if rank == 0:
@@ -332,7 +411,7 @@ def main():
                                      (" + replay_region_kernel<2> and replay_wide_kernel (the escalated replications "
                                       "replayed again up to their first escalated publish, then continued "
                                       "sequentially from there)"
-                                      if hier_esc and hier_esc["escalating_replications"] else ""))
+                                      if hier_esc and hier_esc.get("escalating_replications") else ""))
                                     if args.policy == "EXT_HIER" and N > _abi.HIER_REGION_NODES
                                     else "replay_wide_kernel (statistics inline)" if N > 256
                                     else "replay_kernel (statistics pass fused)"), "kernel_avg_ms": replay_avg_s * 1e3,
@@ -352,7 +431,7 @@ def main():
                       "energy_j": float(energy[0]), "busy_s": summary["busy_s"],
                       "hist_counts": [int(hist[0].sum()), int(hist[1].sum())]},
         }
-        line["roofline"].update(rocprof_kernel_avg(args, line))
+        line["roofline"].update(rocprof_kernel_avg(args, line) if args.full else {"kernel_avg_ms_rocprof": None})
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()
@@ -454,10 +533,13 @@ def bench_c4(args, ctx, dev, dist, world, rank):
     summary = fa.summarize(job)
     hist = out.hist.cpu().numpy()
     decisions = args.R_total * T * args.steps
+    if args.dump_outputs:  # the job record the step returned, the histograms, and the last block's records
+        dump_outputs(args.dump_outputs, rank, world,
+                     records={"rep": out.rep_stats()[:blocks[-1][1]], "job": job}, arrays={"hist": hist})
     # reference-defined decisions (publishes up to each replication's abort tick): the traces were generated
     # inside the replay kernel, so they are regenerated here (untimed) in blocks from the same recipe
     ref_defined = None
-    if len(blocks) == 1:
+    if args.full and len(blocks) == 1:
         abt = torch.from_numpy(np.ascontiguousarray(out.rep_stats()["abort_tick"][:n])).to(dev)
         cnt, G = 0, 8192
         for g0 in range(0, n, G):
@@ -470,7 +552,7 @@ def bench_c4(args, ctx, dev, dist, world, rank):
             dist.all_reduce(tot)
         ref_defined = int(tot.item())
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         # the CPU baseline replays the first block's first replications from the materialised trace; its
         # records must equal the generated replay's (parity)
         nb = min(args.cpu_reps, blocks[0][1])
@@ -485,7 +567,7 @@ def bench_c4(args, ctx, dev, dist, world, rank):
     # committed under profiles/ when it exists for this configuration
     valu = None
     prof = os.path.join(ROOT, "profiles", "pmc_valu_c4.json")
-    if os.path.exists(prof):
+    if args.full and os.path.exists(prof):
         with open(prof) as f:
             pj = json.load(f)
         if pj.get("config") == {"T": T, "N": N, "block": args.block, "ring": args.ring, "policy": args.policy}:
@@ -519,7 +601,8 @@ def bench_c4(args, ctx, dev, dist, world, rank):
                       "response_ms_mean": summary["response_ms"].get("mean"), "energy_j": summary["energy_j"],
                       "max_pending": summary["max_pending"], "hist_counts": [int(hist[0].sum()), int(hist[1].sum())]},
         }
-        line["roofline"].update(rocprof_kernel_avg(args, line))  # (the committed kernel trace of this library)
+        # (the committed kernel trace of this library)
+        line["roofline"].update(rocprof_kernel_avg(args, line) if args.full else {"kernel_avg_ms_rocprof": None})
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()
@@ -578,8 +661,12 @@ def bench_c1(args, ctx, dev, dist, world, rank):
     if dist is not None:
         dist.all_reduce(total)
     decisions, events, failed = (int(x) for x in total.cpu().tolist())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world,
+                     per_task={"node": out.node, "status": out.status, "start_tick": out.start_tick,
+                               "done_tick": out.done_tick}, records={"rep": st})
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib
         reps = min(R, 1024)  # ~10-30 s of single-core work in total
@@ -632,7 +719,8 @@ def bench_c1(args, ctx, dev, dist, world, rank):
             "stats": {"decisions": decisions, "events": events, "local": int(st["n_local"].sum()),
                       "forwarded": int(st["n_forwarded"].sum())},
         }
-        line["roofline"].update(rocprof_kernel_avg(args, line))  # (the committed kernel trace of this library)
+        # (the committed kernel trace of this library)
+        line["roofline"].update(rocprof_kernel_avg(args, line) if args.full else {"kernel_avg_ms_rocprof": None})
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

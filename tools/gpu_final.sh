@@ -30,7 +30,7 @@ case "${PART:-1}" in
   timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke(); print('__SMOKE_OK__')" > $O/smoke.log 2>&1 || { tail $O/smoke.log; exit 1; }
   tail -n 1 $O/smoke.log
   step bench_c3
-  timeout -k 10 400 python bench.py > $O/bench_c3.log 2>&1 || { tail $O/bench_c3.log; exit 1; }
+  timeout -k 10 400 python bench.py --full > $O/bench_c3.log 2>&1 || { tail $O/bench_c3.log; exit 1; }
   grep '^{' $O/bench_c3.log | tail -n 1 > $O/bench_c3.json
   kt c3 replay_kernel 2 || exit 1  # the driver's command: bench.py with its defaults (10 steps, 2 warm-up)
   ;;
@@ -51,10 +51,10 @@ case "${PART:-1}" in
   ;;
 4)
   step bench_c4
-  timeout -k 10 400 python bench.py --workload c4 --steps 3 --warmup 1 > $O/bench_c4.log 2>&1 || { tail $O/bench_c4.log; exit 1; }
+  timeout -k 10 400 python bench.py --full --workload c4 --steps 3 --warmup 1 > $O/bench_c4.log 2>&1 || { tail $O/bench_c4.log; exit 1; }
   grep '^{' $O/bench_c4.log | tail -n 1 > $O/bench_c4.json
   step bench_c1
-  timeout -k 10 400 python bench.py --workload c1 --steps 2 --warmup 1 > $O/bench_c1.log 2>&1 || { tail $O/bench_c1.log; exit 1; }
+  timeout -k 10 400 python bench.py --full --workload c1 --steps 2 --warmup 1 > $O/bench_c1.log 2>&1 || { tail $O/bench_c1.log; exit 1; }
   grep '^{' $O/bench_c1.log | tail -n 1 > $O/bench_c1.json
   ;;
 5)

@@ -6,7 +6,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/fullparity; mkdir -p $O
 run() {  # name, args
-  timeout -k 10 500 python bench.py $2 > $O/$1.log 2>&1 || { tail -20 $O/$1.log; exit 1; }
+  timeout -k 10 500 python bench.py --full $2 > $O/$1.log 2>&1 || { tail -20 $O/$1.log; exit 1; }
   grep '^{' $O/$1.log | tail -n 1 > $O/$1.json
   python3 -c "
 import json; d=json.load(open('$O/$1.json')); c=d['cpu_baseline']
