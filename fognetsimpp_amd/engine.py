@@ -45,6 +45,22 @@ def _stream_ptr(device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _check_out(out, m: int, device):
+    """Caller-supplied pair of int32 [m] result tensors of a batched decision."""
+    a, b = out
+    for t in (a, b):
+        if t.dtype != torch.int32 or tuple(t.shape) != (m,) or t.device != device or not t.is_contiguous():
+            raise FognetError(_abi.FOGNET_ERR_ARG, f"out: a pair of contiguous int32 [{m}] tensors on {device}")
+    return a, b
+
+
+def _check_bytes(t, nbytes: int, device, what: str):
+    """Caller-supplied record buffer: contiguous uint8 of at least nbytes on device."""
+    if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < nbytes or t.device != device or not t.is_contiguous():
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"{what}: a contiguous uint8 tensor of at least {nbytes} B on {device}")
+    return t
+
+
 class Context:
     """A fognet_ctx bound to one HIP device (gfx950 required)."""
 
@@ -136,11 +152,16 @@ class BrokerBaseApp3:
         self.ctx.check(rc, "sendPubAck_window")
         return out
 
-    def sendPubAck_batch(self, adv_busy: torch.Tensor, adv_mips: torch.Tensor, req: torch.Tensor):  # noqa: N802
-        """M independent decisions on device tensors [M, n]; returns (node, status) int32 [M]."""
+    def sendPubAck_batch(self, adv_busy: torch.Tensor, adv_mips: torch.Tensor, req: torch.Tensor,  # noqa: N802
+                         out: tuple[torch.Tensor, torch.Tensor] | None = None):
+        """M independent decisions on device tensors [M, n]; returns (node, status) int32 [M].
+        ``out``: write into these (node, status) tensors instead of new ones."""
         m, n = adv_busy.shape
-        node = torch.empty(m, dtype=torch.int32, device=adv_busy.device)
-        status = torch.empty(m, dtype=torch.int32, device=adv_busy.device)
+        if out is not None:
+            node, status = _check_out(out, m, adv_busy.device)
+        else:
+            node = torch.empty(m, dtype=torch.int32, device=adv_busy.device)
+            status = torch.empty(m, dtype=torch.int32, device=adv_busy.device)
         rc = self.ctx._lib.fognet_decide_batch_dev(
             self.ctx.handle, _abi.FOGNET_POLICY_REF_V3, m, n,
             _ptr(adv_busy.contiguous()), _ptr(adv_mips.contiguous()), _ptr(req.contiguous()),
@@ -173,12 +194,17 @@ class BrokerBaseApp2:
         self.ctx.check(rc, "sendPubAck(v2)")
         return act.value, node.value
 
-    def sendPubAck_batch(self, adv_mips: torch.Tensor, local_mips: torch.Tensor, req: torch.Tensor):  # noqa: N802
+    def sendPubAck_batch(self, adv_mips: torch.Tensor, local_mips: torch.Tensor, req: torch.Tensor,  # noqa: N802
+                         out: tuple[torch.Tensor, torch.Tensor] | None = None):
         """M independent decisions on device tensors adv_mips [M, n], local_mips [M],
-        req [M]; returns (action, node) int32 [M]."""
+        req [M]; returns (action, node) int32 [M].  ``out``: write into these
+        (action, node) tensors instead of new ones."""
         m, n = adv_mips.shape
-        node = torch.empty(m, dtype=torch.int32, device=adv_mips.device)
-        act = torch.empty(m, dtype=torch.int32, device=adv_mips.device)
+        if out is not None:
+            act, node = _check_out(out, m, adv_mips.device)
+        else:
+            node = torch.empty(m, dtype=torch.int32, device=adv_mips.device)
+            act = torch.empty(m, dtype=torch.int32, device=adv_mips.device)
         rc = self.ctx._lib.fognet_decide_v2_batch_dev(
             self.ctx.handle, m, n, _ptr(adv_mips.contiguous()), _ptr(local_mips.contiguous()), _ptr(req.contiguous()),
             _ptr(node), _ptr(act), _stream_ptr(adv_mips.device))
@@ -331,12 +357,14 @@ def run_generated(ctx: Context, seed: int, R: int, T: int, N: int, mean_gap_tick
     return out
 
 
-def user_stats(ctx: Context, trace: dict, out: BatchResult, user_ul, user_dl) -> np.ndarray:
+def user_stats(ctx: Context, trace: dict, out: BatchResult, user_ul, user_dl,
+               res: torch.Tensor | None = None) -> np.ndarray:
     """User-side signals (fognet_user_stats_dev) of a finished replay: broker
     ``delay`` and mqttApp2's ``latency`` / ``latencyH1`` / ``taskTime`` as exact
     tick moments per replication (USER_STATS_DTYPE [R]).  ``user_ul`` /
     ``user_dl``: the publishing user's links, [R] (one user per replication)
-    or [R, T] (per task), host arrays or device tensors."""
+    or [R, T] (per task), host arrays or device tensors.  ``res``: the device
+    buffer the records are written to (uint8, R * sizeof(fognet_user_stats))."""
     arrive = trace["arrive"]
     R, T = arrive.shape
     dev = arrive.device
@@ -351,7 +379,11 @@ def user_stats(ctx: Context, trace: dict, out: BatchResult, user_ul, user_dl) ->
                                                f"{tuple(uu.shape)} / {tuple(ud.shape)}")
     mips = trace["mips"]
     N = mips.shape[-1]
-    res = torch.zeros(R * _abi.USER_STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    nres = R * _abi.USER_STATS_DTYPE.itemsize
+    if res is None:
+        res = torch.zeros(nres, dtype=torch.uint8, device=dev)
+    else:
+        _check_bytes(res, nres, dev, "res")
     bi = _abi.BatchIn(R, T, N, _abi.FOGNET_POLICY_REF_V3, N if mips.dim() == 2 else 0, 0,
                       _ptr(arrive), _ptr(trace["req"]), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
                       _ptr(trace["init"]), None, None)
@@ -359,7 +391,7 @@ def user_stats(ctx: Context, trace: dict, out: BatchResult, user_ul, user_dl) ->
                        _ptr(out.stats), None, None)
     ctx.check(ctx._lib.fognet_user_stats_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(uu), _ptr(ud), per_task,
                                              _ptr(res), _stream_ptr(dev)), "user_stats")
-    return res.cpu().numpy().view(_abi.USER_STATS_DTYPE)
+    return res[:nres].cpu().numpy().view(_abi.USER_STATS_DTYPE)
 
 
 @dataclass
@@ -375,12 +407,14 @@ class V2Result:
 
 
 def run_v2(ctx: Context, trace: dict, broker_mips, stop_tick, required_time_s=0.01, queue_capacity: int = 0,
-           stream=None) -> V2Result:
+           stream=None, out: V2Result | None = None) -> V2Result:
     """R replays of the v2 model (BrokerBaseApp2 + ComputeBrokerApp2, the modules
     simulations/example/wirelessNet.ini:56,62 select) on the device
     (fognet_run_v2_dev).  ``trace``: device tensors arrive/req [R, T], node
     parameters mips/dl/ul and first_adv (first ADVERTISEMIPS firing) [R, N] or
-    [N]; ``broker_mips``, ``stop_tick``, ``required_time_s``: scalars or [R]."""
+    [N]; ``broker_mips``, ``stop_tick``, ``required_time_s``: scalars or [R]
+    (host values, or device tensors [R] of the ABI dtype, used as they are).
+    ``out``: write into these buffers (V2Result layout) instead of new ones."""
     arrive, req = trace["arrive"], trace["req"]
     R, T = arrive.shape
     dev = arrive.device
@@ -389,11 +423,26 @@ def run_v2(ctx: Context, trace: dict, broker_mips, stop_tick, required_time_s=0.
     for k in ("dl", "ul", "first_adv"):
         if tuple(trace[k].shape) != tuple(mips.shape):
             raise FognetError(_abi.FOGNET_ERR_ARG, f"{k} has shape {tuple(trace[k].shape)}, mips {tuple(mips.shape)}")
-    per = lambda v, dt: torch.as_tensor(np.array(np.broadcast_to(np.asarray(v), (R,))), dtype=dt).to(dev)
+    def per(v, dt):
+        if isinstance(v, torch.Tensor):
+            if v.dtype != dt or tuple(v.shape) != (R,) or v.device != dev or not v.is_contiguous():
+                raise FognetError(_abi.FOGNET_ERR_ARG, f"per-replication tensor: contiguous {dt} [{R}] on {dev}")
+            return v
+        return torch.as_tensor(np.array(np.broadcast_to(np.asarray(v), (R,))), dtype=dt).to(dev)
     bm, st_, rt = per(broker_mips, torch.int32), per(stop_tick, torch.int64), per(required_time_s, torch.float64)
-    out = V2Result(torch.empty((R, T), dtype=torch.int32, device=dev), torch.empty((R, T), dtype=torch.uint8, device=dev),
-                   torch.empty((R, T), dtype=torch.int64, device=dev), torch.empty((R, T), dtype=torch.int64, device=dev),
-                   torch.zeros(R * _abi.V2_STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev))
+    if out is None:
+        out = V2Result(torch.empty((R, T), dtype=torch.int32, device=dev),
+                       torch.empty((R, T), dtype=torch.uint8, device=dev),
+                       torch.empty((R, T), dtype=torch.int64, device=dev),
+                       torch.empty((R, T), dtype=torch.int64, device=dev),
+                       torch.zeros(R * _abi.V2_STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev))
+    else:
+        for k, dt in (("node", torch.int32), ("status", torch.uint8), ("start_tick", torch.int64),
+                      ("done_tick", torch.int64)):
+            t = getattr(out, k)
+            if t.dtype != dt or tuple(t.shape) != (R, T) or t.device != dev or not t.is_contiguous():
+                raise FognetError(_abi.FOGNET_ERR_ARG, f"out.{k}: contiguous {dt} [{R}, {T}] on {dev}")
+        _check_bytes(out.stats, R * _abi.V2_STATS_DTYPE.itemsize, dev, "out.stats")
     vi = _abi.V2In(R, T, N, N if mips.dim() == 2 else 0, queue_capacity, 0, _ptr(arrive), _ptr(req), _ptr(bm), _ptr(rt),
                    _ptr(st_), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]), _ptr(trace["first_adv"]))
     vo = _abi.V2Out(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick), _ptr(out.stats))
@@ -430,12 +479,17 @@ def summarize_moments(m, raw_ms: bool = True) -> dict:
     return d
 
 
-def reduce_stats(ctx: Context, stats: torch.Tensor, R: int) -> np.ndarray:
-    """Exact job-level reduction on the device; returns a JOB_STATS_DTYPE record."""
-    out = torch.zeros(_abi.JOB_STATS_DTYPE.itemsize, dtype=torch.uint8, device=stats.device)
+def reduce_stats(ctx: Context, stats: torch.Tensor, R: int, out: torch.Tensor | None = None) -> np.ndarray:
+    """Exact job-level reduction on the device; returns a JOB_STATS_DTYPE record.
+    ``out``: the device buffer the record is written to (uint8, sizeof(fognet_job_stats))."""
+    nout = _abi.JOB_STATS_DTYPE.itemsize
+    if out is None:
+        out = torch.zeros(nout, dtype=torch.uint8, device=stats.device)
+    else:
+        _check_bytes(out, nout, stats.device, "out")
     ctx.check(ctx._lib.fognet_reduce_stats_dev(ctx.handle, _ptr(stats), R, _ptr(out), _stream_ptr(stats.device)),
               "reduce_stats")
-    return out.cpu().numpy().view(_abi.JOB_STATS_DTYPE)[0]
+    return out[:nout].cpu().numpy().view(_abi.JOB_STATS_DTYPE)[0]
 
 
 def merge_job_stats(records) -> np.ndarray:

@@ -279,6 +279,28 @@ typedef struct fognet_batch_out {
                                  (the caller zeroes it; nullable)                                 */
 } fognet_batch_out;
 
+/* Buffers.  What every *_dev entry point asks of, and leaves in, the caller's arrays
+ * (tests/test_buffer_contract_gpu.py holds the library to each sentence):
+ *   Alignment.  Every pointer needs only the natural alignment of its element type
+ *     (8 B for int64 / double / the record structs, 4 B for int32, 1 B for status).
+ *   Bounds.  Nothing outside [R][T] / [R|1][N] / [R] / [m] / hist is read or written,
+ *     whatever T % 64, R % 4 (the v2 wavefronts) or R % 4096 (the reduction) are.
+ *   Initialisation.  No output needs initialising, and none depends on what it held
+ *     before the call, except hist, which is ADDED to (the caller zeroes it once).
+ *   A failed replication (stats[r].status other than FOGNET_OK / FOGNET_REF_ABORTED) never
+ *     touches its neighbours.  Its per-task rows and its node_energy_j row are undefined.
+ *     Its record is written in full: status, and n_tasks, events and max_pending up to the
+ *     failure; the other fields (and what it added to hist) cover the n_tasks publishes
+ *     decided before the failure and are no result.  A replication refused before its first
+ *     decision (n_tasks = 0: every precondition on the node parameters, and a bad publish
+ *     in a chunk the replay checks before it decides) therefore has the empty-set values
+ *     used throughout this header: counts and sums 0, energy_j 0.0, minima INT64_MAX,
+ *     maxima (last_tick too) INT64_MIN, abort_tick = INT64_MAX, abort_task = -1.
+ *     (fognet_replay_dev alone writes only the four fields named at its declaration;
+ *     fognet_rep_stats_dev completes the record.)  Likewise fognet_v2_stats (every count 0
+ *     for a replication refused before its first event) and fognet_user_stats (the
+ *     count == 0 values of fognet_moments for a replication with n_tasks = 0). */
+
 /* count / min / max / exact signed 128-bit sum and 192-bit sum of squares of a
  * signal's raw emitted values (min_raw = INT64_MAX, max_raw = INT64_MIN when
  * count == 0); overflow: emissions lost to the simtime_t range (see above). */
