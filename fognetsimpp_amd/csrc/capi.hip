@@ -55,7 +55,7 @@ constexpr int kDefaultRing = 2048;
 // register kernel hands over (at most one wave per SIMD of the chip).
 constexpr int32_t kWideFallbackSlots = 1024;
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+using fognet::align256;
 
 int fail(fognet_ctx* c, int rc, const std::string& msg) {
   if (c) c->err = msg;
@@ -170,41 +170,26 @@ int prepare(fognet_ctx* c, const fognet_batch_in* in, fognet::ReplayArgs* a, boo
   return FOGNET_OK;
 }
 
-// N > 256 takes the wide replay kernel (replay_wide.hip); FOGNET_REPLAY_KERNEL=wide
-// forces it for any N (used by the parity tests to check both kernels).
-// FOGNET_REPLAY_STATS=inloop: the statistics of a fused replay come from
-// in-loop accumulators (replay_inl_kernel, 3 waves/SIMD) instead of the
-// epilogue's re-read of the outputs (replay_kernel, 4 waves/SIMD); the records
-// are identical (the parity tests run both).  Not the default: at C3 (4,096
-// replications, all resident at 4 waves/SIMD) it measured 20.9 ms/launch
-// against 14.1 ms, the fourth wave per SIMD being worth more than the re-read.
-// FOGNET_HIER_REGIONS=0: EXT_HIER replays run on the sequential wide kernel
-// only; =only: the region pass without the sequential hand-over (a replication
-// it cannot finish keeps an internal status) -- the parity tests use both to
-// check that each path ran.
-bool use_regions() {
-  const char* f = getenv("FOGNET_HIER_REGIONS");
-  return f == nullptr || strcmp(f, "0") != 0;
-}
-bool regions_auto() { return getenv("FOGNET_HIER_REGIONS") == nullptr; }
-// FOGNET_HIER_RESUME=0: an escalated replication is replayed by the sequential kernel from the
-// start (and the automatic mode below chooses between the two paths); default: it continues from
-// its first escalated publish (replay_region.hip)
-bool use_resume() {
-  const char* f = getenv("FOGNET_HIER_RESUME");
-  return f == nullptr || strcmp(f, "0") != 0;
-}
-// automatic mode: after a region pass that handed most replications over, this many launches go
-// straight to the sequential replay before a region pass measures again
-constexpr int kHierReprobe = 15;
-bool regions_only() {
-  const char* f = getenv("FOGNET_HIER_REGIONS");
-  return f != nullptr && strcmp(f, "only") == 0;
+// The environment switches, each read once in every call (the parity tests flip them between calls to
+// check that each path ran).  FOGNET_REPLAY_KERNEL=wide: the wide replay kernel (replay_wide.hip),
+// which N > 256 takes anyway, for any N.
+// FOGNET_REPLAY_STATS=inloop: the statistics of a fused replay come from in-loop accumulators
+// (replay_inl_kernel, 3 waves/SIMD) instead of the epilogue's re-read of the outputs (replay_kernel,
+// 4 waves/SIMD); the records are identical (the parity tests run both).  Not the default: at C3 (4,096
+// replications, all resident at 4 waves/SIMD) it measured 20.9 ms/launch against 14.1 ms, the fourth
+// wave per SIMD being worth more than the re-read.
+// FOGNET_HIER_REGIONS=0: EXT_HIER replays run on the sequential wide kernel only; =only: the region pass
+// without the sequential hand-over (a replication it cannot finish keeps an internal status).
+// FOGNET_HIER_RESUME=0: an escalated replication is replayed by the sequential kernel from the start (and
+// with FOGNET_HIER_REGIONS unset hier_skip_regions chooses between the two paths); default: it continues
+// from its first escalated publish (replay_region.hip)
+bool env_is(const char* name, const char* value) {
+  const char* f = getenv(name);
+  return f != nullptr && strcmp(f, value) == 0;
 }
 
-bool use_inloop() {
-  const char* f = getenv("FOGNET_REPLAY_STATS");
-  return f != nullptr && strcmp(f, "inloop") == 0;
+bool use_wide(int32_t N) {
+  return N > fognet::kWave * fognet::kMaxNodesPerLane || env_is("FOGNET_REPLAY_KERNEL", "wide");
 }
 
 // Workspace slots of the hand-over launch: the wide kernel walks the hand-over
@@ -220,10 +205,194 @@ int32_t fallback_slots(int32_t R, int32_t T, int32_t N, size_t ring_bytes, bool 
   return slots;
 }
 
-bool use_wide(int32_t N) {
-  if (N > fognet::kWave * fognet::kMaxNodesPerLane) return true;
-  const char* f = getenv("FOGNET_REPLAY_KERNEL");
-  return f != nullptr && strcmp(f, "wide") == 0;
+// Sizes a layout of workspace.h (parts: the walk over its part list, returning the total), grows
+// the context's one workspace allocation to hold it and sets the parts' pointers.
+template <class Parts>
+int carve(fognet_ctx* c, const char* what, Parts parts) {
+  fognet::WsCursor size{nullptr};
+  const int rc = ensure(c, (void**)&c->ring, &c->ring_bytes, parts(size), what);
+  fognet::WsCursor bind{reinterpret_cast<unsigned char*>(c->ring)};
+  if (rc == FOGNET_OK) parts(bind);
+  return rc;
+}
+
+// The wide kernel on its own: workgroup r replays replication r.
+int run_wide(fognet_ctx* c, const fognet::ReplayArgs& a, hipStream_t s) {
+  const size_t ws = fognet::replay_wide_workspace_bytes(a.R, a.T, a.N, a.gen_on != 0, a.policy);
+  const int rc = ensure(c, (void**)&c->ring, &c->ring_bytes, ws, "wide replay workspace");
+  if (rc) return rc;
+  const hipError_t e = fognet::launch_replay_wide(a, c->ring, a.R, s);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "wide replay launch");
+}
+
+// Automatic EXT_HIER path choice (restart mode, FOGNET_HIER_REGIONS unset): after a region pass that
+// handed most replications over, this many launches go straight to the sequential replay before a
+// region pass measures again
+constexpr int kHierReprobe = 15;
+
+// Takes in the last region pass's hand-over count, if it has reached the host (never waited for),
+// and says whether this launch skips the region pass.
+bool hier_skip_regions(fognet_ctx* c, const fognet_ctx::HierShape& shape) {
+  if (c->hier_pending && hipEventQuery(c->hier_ev) == hipSuccess) {
+    c->hier_pending = false;
+    c->hier_seq = 2 * (int64_t)c->hier_host[0] > (int64_t)c->hier_pend_shape.R;
+    c->hier_seq_shape = c->hier_pend_shape;
+    c->hier_seq_runs = 0;
+  }
+  if (c->hier_seq && !(c->hier_seq_shape == shape)) c->hier_seq = false;  // another job: measure it
+  if (c->hier_seq && c->hier_seq_runs < kHierReprobe) {
+    ++c->hier_seq_runs;  // most replications escalated: the region pass would only be replayed again
+    return true;
+  }
+  c->hier_seq = false;  // (measure again)
+  return false;
+}
+
+// The hand-over count of the region pass just launched back to the host, asynchronously.  While a
+// measurement is in flight, later launches are not measured: its pinned slot and event stay paired
+// with the launch that issued them.
+int hier_measure(fognet_ctx* c, const fognet_ctx::HierShape& shape, const int32_t* count, hipStream_t s) {
+  if (c->hier_pending) return FOGNET_OK;
+  if (!c->hier_host && hipHostMalloc((void**)&c->hier_host, sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
+    c->hier_host = nullptr;
+  if (!c->hier_ev && hipEventCreateWithFlags(&c->hier_ev, hipEventDisableTiming) != hipSuccess) c->hier_ev = nullptr;
+  if (!c->hier_host || !c->hier_ev) return FOGNET_OK;
+  c->hier_pend_shape = shape;
+  hipError_t e = hipMemcpyAsync(c->hier_host, count, sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipEventRecord(c->hier_ev, s);
+  if (e != hipSuccess) return hip_fail(c, e, "hand-over count copy");
+  c->hier_pending = true;
+  return FOGNET_OK;
+}
+
+// EXT_HIER by region: one wavefront per (replication, region) while no region escalates (replay_region.hip),
+// the statistics pass, then the sequential wide kernel for the replications some region handed back, with one
+// workspace slot each up to kWideFallbackSlots (an escalation-heavy job replays its hand-overs side by side, as
+// the sequential-only path does).  only: FOGNET_HIER_REGIONS=only; measure (nullable): for the automatic choice
+int run_regions(fognet_ctx* c, fognet::ReplayArgs& a, int32_t B, bool resume, bool only,
+                const fognet_ctx::HierShape* measure, hipStream_t s) {
+  const int32_t slots = a.R < kWideFallbackSlots ? a.R : kWideFallbackSlots;
+  const size_t fb = fognet::replay_wide_workspace_bytes(slots, a.T, a.N, false, a.policy);
+  fognet::ReplayWs h;
+  fognet::RegionWs w;
+  const int rc = carve(c, "region replay workspace", [&](fognet::WsCursor& v) {
+    return fognet::region_ws(h, w, a.R, a.T, a.N, B, fb, resume, v);
+  });
+  if (rc) return rc;
+  w.pass = 1;
+  w.B = B;
+  a.wide_count = h.count;
+  a.wide_list = only ? nullptr : h.list;
+  hipError_t e = hipMemsetAsync(a.wide_count, 0, sizeof(int32_t), s);
+  if (e != hipSuccess) return hip_fail(c, e, "hand-over counter");
+  e = fognet::launch_replay_region(a, w, resume && !only, s);
+  if (e != hipSuccess) return hip_fail(c, e, "region replay launch");
+  if (only) return FOGNET_OK;
+  e = fognet::launch_replay_wide(a, h.body, slots, s, resume ? &w : nullptr);
+  if (e != hipSuccess) return hip_fail(c, e, "wide hand-over launch");
+  return measure ? hier_measure(c, *measure, a.wide_count, s) : FOGNET_OK;
+}
+
+// The register kernel (replay.hip), then the wide kernel for the replications it handed over
+// (usually none: every workgroup leaves at once).
+int run_register(fognet_ctx* c, fognet::ReplayArgs& a, bool stats_only, hipStream_t s) {
+  const size_t ring_bytes = (size_t)a.R * (size_t)a.N * ((size_t)1 << a.q_log2) * sizeof(fognet::RingWord);
+  const int32_t slots = fallback_slots(a.R, a.T, a.N, ring_bytes, false, a.policy);
+  const size_t fb_bytes = fognet::replay_wide_workspace_bytes(slots, a.T, a.N, false, a.policy);
+  const bool scratch_out = stats_only && !a.inloop;  // the fused statistics epilogue reads the outputs back
+  fognet::ReplayWs w;
+  const int rc = carve(c, "ring workspace", [&](fognet::WsCursor& v) {
+    return fognet::register_ws(w, a.R, ring_bytes, fb_bytes, scratch_out ? (size_t)a.R * (size_t)a.T : 0, v);
+  });
+  if (rc) return rc;
+  a.wide_count = w.count;
+  a.wide_list = w.list;
+  a.ring = reinterpret_cast<fognet::RingWord*>(w.body);
+  if (scratch_out) {
+    a.out_node = w.out_node;
+    a.out_status = w.out_status;
+    a.out_start = w.out_start;
+    a.out_done = w.out_done;
+  }
+  hipError_t e = hipMemsetAsync(a.wide_count, 0, sizeof(int32_t), s);
+  if (e != hipSuccess) return hip_fail(c, e, "hand-over counter");
+  if (!a.inloop) {  // replay_kernel's progress board: every slot empty
+    a.board = w.board;
+    e = hipMemsetAsync(a.board, 0xFF, fognet::kBoardWords * sizeof(uint32_t), s);
+    if (e != hipSuccess) return hip_fail(c, e, "progress board");
+  }
+  e = fognet::launch_replay(a, s);
+  if (e != hipSuccess) return hip_fail(c, e, "replay launch");
+  // The wide kernel accumulates its statistics inline; in a replay-only call the statistics stage that
+  // follows recomputes them for every replication from the per-task outputs, so the hand-over must not
+  // add its histogram and energy as well
+  fognet::ReplayArgs hw = a;
+  if (!a.fuse_stats) {
+    hw.hist = nullptr;
+    hw.out_energy = nullptr;
+  }
+  e = fognet::launch_replay_wide(hw, w.body, slots, s);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "wide hand-over launch");
+}
+
+int run_rep_stats(fognet_ctx* c, const fognet::ReplayArgs& a, hipStream_t s) {
+  const hipError_t e = fognet::launch_rep_stats(a, s);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "stats launch");
+}
+
+// which: 1 replay, 2 statistics, 3 both (fused).  Validation and routing only.
+int stage(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_out* out, void* stream, int which) {
+  if (!c || !out) return FOGNET_ERR_ARG;
+  fognet::ReplayArgs a;
+  int rc = prepare(c, in, &a);
+  if (rc) return rc;
+  if (!out->stats) return fail(c, FOGNET_ERR_ARG, "stats output is required (per-replication status)");
+  const int n_null = !out->node + !out->status + !out->start_tick + !out->done_tick;
+  if (n_null != 0 && n_null != 4)
+    return fail(c, FOGNET_ERR_ARG, "per-task outputs: give all four arrays, or none (statistics only)");
+  const bool stats_only = n_null == 4 && a.T > 0;
+  if (stats_only && which != 3)
+    return fail(c, FOGNET_ERR_UNSUPPORTED, "statistics-only replays run through fognet_run_batch_dev");
+  if (a.R == 0) return FOGNET_OK;
+  rc = set_device(c);
+  if (rc) return rc;
+  a.out_node = out->node;
+  a.out_status = out->status;
+  a.out_start = out->start_tick;
+  a.out_done = out->done_tick;
+  a.out_stats = out->stats;
+  a.out_energy = out->node_energy_j;
+  a.hist = out->hist;
+  if (a.out_energy && !a.p_busy) return fail(c, FOGNET_ERR_ARG, "node_energy_j needs the power model (p_busy_w/p_idle_w)");
+  const hipStream_t s = (hipStream_t)stream;
+  if (use_wide(a.N) || a.down || a.policy == FOGNET_POLICY_EXT_HIER) {  // (regions: the wide kernel's groups)
+    // crashes are only modelled by the wide kernel; it accumulates the statistics while it replays, so the
+    // statistics-only stage has nothing left to do
+    if (!(which & 1)) return FOGNET_OK;
+    a.no_task_out = stats_only ? 1 : 0;
+    const int32_t B = (a.N + FOGNET_HIER_REGION_NODES - 1) / FOGNET_HIER_REGION_NODES;
+    const bool hier_split = a.policy == FOGNET_POLICY_EXT_HIER && !a.down && !stats_only && a.T > 0 && B >= 2;
+    const char* const mode = getenv("FOGNET_HIER_REGIONS");
+    bool regions = hier_split && (mode == nullptr || strcmp(mode, "0") != 0);
+    // resume: the region pass is never wasted and is always taken
+    const bool resume = regions && !env_is("FOGNET_HIER_RESUME", "0");
+    const bool automatic = regions && mode == nullptr && !resume;
+    const fognet_ctx::HierShape shape{a.R, a.T, a.N, stream};
+    if (automatic && hier_skip_regions(c, shape)) regions = false;
+    if (hier_split) ++(regions ? c->hier_region_launches : c->hier_seq_launches);
+    if (!regions) return run_wide(c, a, s);
+    const bool only = mode != nullptr && strcmp(mode, "only") == 0;
+    return run_regions(c, a, B, resume, only, automatic ? &shape : nullptr, s);
+  }
+  // both stages: the replay kernel runs the statistics pass as its epilogue
+  a.fuse_stats = which == 3 ? 1 : 0;
+  if (a.fuse_stats) which = 1;
+  // statistics accumulated in the loop (replay_inl_kernel) where the node tails hold exact totals
+  a.inloop = a.fuse_stats && (uint64_t)a.T * (uint64_t)a.max_s < (1ull << 32) && env_is("FOGNET_REPLAY_STATS", "inloop");
+  if (a.inloop) a.no_task_out = stats_only ? 1 : 0;
+  if (which & 1) rc = run_register(c, a, stats_only, s);
+  if (rc == FOGNET_OK && (which & 2)) rc = run_rep_stats(c, a, s);
+  return rc;
 }
 
 }  // namespace
@@ -441,209 +610,6 @@ int fognet_decide_v2(fognet_ctx* c, int32_t n, const int32_t* adv_mips, int32_t 
   return FOGNET_OK;
 }
 
-static int stage(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_out* out, void* stream, int which) {
-  if (!c || !out) return FOGNET_ERR_ARG;
-  fognet::ReplayArgs a;
-  int rc = prepare(c, in, &a);
-  if (rc) return rc;
-  if (!out->stats) return fail(c, FOGNET_ERR_ARG, "stats output is required (per-replication status)");
-  const int n_null = !out->node + !out->status + !out->start_tick + !out->done_tick;
-  if (n_null != 0 && n_null != 4)
-    return fail(c, FOGNET_ERR_ARG, "per-task outputs: give all four arrays, or none (statistics only)");
-  const bool stats_only = n_null == 4 && a.T > 0;
-  if (stats_only && which != 3)
-    return fail(c, FOGNET_ERR_UNSUPPORTED, "statistics-only replays run through fognet_run_batch_dev");
-  if (a.R == 0) return FOGNET_OK;
-  rc = set_device(c);
-  if (rc) return rc;
-  a.out_node = out->node;
-  a.out_status = out->status;
-  a.out_start = out->start_tick;
-  a.out_done = out->done_tick;
-  a.out_stats = out->stats;
-  a.out_energy = out->node_energy_j;
-  a.hist = out->hist;
-  if (a.out_energy && !a.p_busy) return fail(c, FOGNET_ERR_ARG, "node_energy_j needs the power model (p_busy_w/p_idle_w)");
-  hipError_t e = hipSuccess;
-  if (use_wide(a.N) || a.down || a.policy == FOGNET_POLICY_EXT_HIER) {  // (regions: the wide kernel's groups)
-    // crashes are only modelled by the wide kernel; it accumulates the statistics while it replays, so the
-    // statistics-only stage has nothing left to do
-    if (!(which & 1)) return FOGNET_OK;
-    a.no_task_out = stats_only ? 1 : 0;
-    const int32_t B = (a.N + FOGNET_HIER_REGION_NODES - 1) / FOGNET_HIER_REGION_NODES;
-    const bool hier_split = a.policy == FOGNET_POLICY_EXT_HIER && !a.down && !stats_only && a.T > 0 && B >= 2;
-    bool regions = hier_split && use_regions();
-    // resume (replay_region.hip): an escalated replication continues on the sequential kernel from
-    // its first escalated publish, so the region pass is never wasted and is always taken
-    const bool resume = regions && use_resume();
-    const fognet_ctx::HierShape shape{a.R, a.T, a.N, stream};
-    if (regions && regions_auto() && !resume) {
-      // the last region pass's hand-over count, if it has reached the host (never waited for)
-      if (c->hier_pending && hipEventQuery(c->hier_ev) == hipSuccess) {
-        c->hier_pending = false;
-        c->hier_seq = 2 * (int64_t)c->hier_host[0] > (int64_t)c->hier_pend_shape.R;
-        c->hier_seq_shape = c->hier_pend_shape;
-        c->hier_seq_runs = 0;
-      }
-      if (c->hier_seq && !(c->hier_seq_shape == shape)) c->hier_seq = false;  // another job: measure it
-      if (c->hier_seq && c->hier_seq_runs < kHierReprobe) {
-        regions = false;  // most replications escalated: the region pass would only be replayed again
-        ++c->hier_seq_runs;
-      } else {
-        c->hier_seq = false;  // (measure again)
-      }
-    }
-    if (hier_split) ++(regions ? c->hier_region_launches : c->hier_seq_launches);
-    if (regions) {
-      // one wavefront per (replication, region) while no region escalates (replay_region.hip), the
-      // statistics pass, then the sequential wide kernel for the replications some region handed back.
-      // workspace: [hand-over counter | list [R] | first escalations [R] | region records [R][B] | segment
-      // offsets [R][B+1] | dispatch keys [R][B] | dispatch order [R*B] | resume records [R] | node tails
-      // [R][N][2] | entries [R][T] | node records [R][N] | busy view [R][B][1024] | region-sorted trace and
-      // outputs [R][T] | sorted -> trace index [R][T]] + the hand-over launch's space, after it (resume: the
-      // wide kernel reads the region state), else from the entries on (stream order: after the finish
-      // kernel has read the node records and the sorted outputs), with one workspace slot per handed-over
-      // replication up to kWideFallbackSlots (an escalation-heavy job replays its hand-overs side by side,
-      // as the sequential-only path does)
-      const size_t RT = (size_t)a.R * (size_t)a.T;
-      const size_t o_esc = align256(256 + (size_t)a.R * sizeof(int32_t));
-      const size_t o_rec = o_esc + align256((size_t)a.R * sizeof(int32_t));
-      const size_t o_seg = o_rec + align256((size_t)a.R * (size_t)B * sizeof(fognet::RegionRec));
-      const size_t o_ok = o_seg + align256((size_t)a.R * (size_t)(B + 1) * sizeof(int32_t));
-      const size_t o_perm = o_ok + align256((size_t)a.R * (size_t)B * sizeof(uint32_t));
-      const size_t o_pacc = o_perm + align256((size_t)a.R * (size_t)B * sizeof(int32_t));
-      const size_t o_tails = o_pacc + align256((size_t)a.R * fognet::kRegionResumeBytes);
-      const size_t o_e = o_tails + align256((size_t)a.R * (size_t)a.N * 2 * sizeof(int64_t));
-      const size_t o_nd = o_e + align256(RT * sizeof(fognet::WideEntry));
-      const size_t o_vb = o_nd + align256((size_t)a.R * (size_t)a.N * sizeof(fognet::WideNode));
-      const size_t o_sa = o_vb + align256((size_t)a.R * (size_t)B * FOGNET_HIER_REGION_NODES * sizeof(uint32_t));
-      const size_t o_sq = o_sa + align256(RT * sizeof(int64_t));
-      const size_t o_inv = o_sq + align256(RT * sizeof(int32_t));
-      const size_t o_on = o_inv + align256(RT * sizeof(int32_t));
-      const size_t o_os = o_on + align256(RT * sizeof(int32_t));
-      const size_t o_ost = o_os + align256(RT);
-      const size_t o_od = o_ost + align256(RT * sizeof(int64_t));
-      const size_t o_sidx = o_od + align256(RT * sizeof(int64_t));
-      const size_t body = o_sidx + align256(RT * sizeof(int32_t)) - o_e;
-      const int32_t slots = a.R < kWideFallbackSlots ? a.R : kWideFallbackSlots;
-      const size_t fb = fognet::replay_wide_workspace_bytes(slots, a.T, a.N, false, a.policy);
-      const size_t o_wide = resume ? o_e + body : o_e;
-      const size_t total = resume ? o_wide + fb : o_e + (body > fb ? body : fb);
-      rc = ensure(c, (void**)&c->ring, &c->ring_bytes, total, "region replay workspace");
-      if (rc) return rc;
-      unsigned char* const base = reinterpret_cast<unsigned char*>(c->ring);
-      a.wide_count = reinterpret_cast<int32_t*>(base);
-      a.wide_list = reinterpret_cast<int32_t*>(base + 256);
-      e = hipMemsetAsync(a.wide_count, 0, sizeof(int32_t), (hipStream_t)stream);
-      if (e != hipSuccess) return hip_fail(c, e, "hand-over counter");
-      fognet::RegionWs w;
-      w.e = reinterpret_cast<fognet::WideEntry*>(base + o_e);
-      w.nd = reinterpret_cast<fognet::WideNode*>(base + o_nd);
-      w.rec = reinterpret_cast<fognet::RegionRec*>(base + o_rec);
-      w.vb = reinterpret_cast<uint32_t*>(base + o_vb);
-      w.esc = reinterpret_cast<int32_t*>(base + o_esc);  // (set by the sort kernel)
-      w.s_idx = reinterpret_cast<int32_t*>(base + o_sidx);
-      w.pacc = base + o_pacc;
-      w.pass = 1;
-      w.seg = reinterpret_cast<int32_t*>(base + o_seg);
-      w.okey = reinterpret_cast<uint32_t*>(base + o_ok);
-      w.perm = reinterpret_cast<int32_t*>(base + o_perm);
-      w.tails = reinterpret_cast<int64_t*>(base + o_tails);
-      w.s_arr = reinterpret_cast<int64_t*>(base + o_sa);
-      w.s_req = reinterpret_cast<int32_t*>(base + o_sq);
-      w.inv = reinterpret_cast<int32_t*>(base + o_inv);
-      w.o_node = reinterpret_cast<int32_t*>(base + o_on);
-      w.o_status = reinterpret_cast<uint8_t*>(base + o_os);
-      w.o_start = reinterpret_cast<int64_t*>(base + o_ost);
-      w.o_done = reinterpret_cast<int64_t*>(base + o_od);
-      w.B = B;
-      if (regions_only()) a.wide_list = nullptr;
-      e = fognet::launch_replay_region(a, w, resume && !regions_only(), (hipStream_t)stream);
-      if (e != hipSuccess) return hip_fail(c, e, "region replay launch");
-      if (regions_only()) return FOGNET_OK;
-      e = fognet::launch_replay_wide(a, base + o_wide, slots, (hipStream_t)stream, resume ? &w : nullptr);
-      if (e != hipSuccess) return hip_fail(c, e, "wide hand-over launch");
-      if (regions_auto() && !resume && !c->hier_pending) {  // the hand-over count back to the host, asynchronously
-        // (while a measurement is in flight, later launches are not measured: its pinned slot and event
-        // stay paired with the launch that issued them)
-        if (!c->hier_host && hipHostMalloc((void**)&c->hier_host, sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
-          c->hier_host = nullptr;
-        if (!c->hier_ev && hipEventCreateWithFlags(&c->hier_ev, hipEventDisableTiming) != hipSuccess) c->hier_ev = nullptr;
-        if (c->hier_host && c->hier_ev) {
-          c->hier_pend_shape = shape;
-          e = hipMemcpyAsync(c->hier_host, a.wide_count, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
-          if (e == hipSuccess) e = hipEventRecord(c->hier_ev, (hipStream_t)stream);
-          if (e != hipSuccess) return hip_fail(c, e, "hand-over count copy");
-          c->hier_pending = true;
-        }
-      }
-      return FOGNET_OK;
-    }
-    const size_t ws = fognet::replay_wide_workspace_bytes(a.R, a.T, a.N, false, a.policy);
-    rc = ensure(c, (void**)&c->ring, &c->ring_bytes, ws, "wide replay workspace");
-    if (rc) return rc;
-    e = fognet::launch_replay_wide(a, c->ring, a.R, (hipStream_t)stream);
-    return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "wide replay launch");
-  }
-  // both stages: the replay kernel runs the statistics pass as its epilogue
-  a.fuse_stats = which == 3 ? 1 : 0;
-  if (a.fuse_stats) which = 1;
-  // statistics accumulated in the loop (replay_inl_kernel) where the node tails hold exact totals
-  a.inloop = a.fuse_stats && (uint64_t)a.T * (uint64_t)a.max_s < (1ull << 32) && use_inloop() ? 1 : 0;
-  if (a.inloop) a.no_task_out = stats_only ? 1 : 0;
-  if (which & 1) {
-    // workspace: [hand-over counter | hand-over list [R] | pending-task rings, reused by the wide kernel's
-    // replay of the handed-over replications once the register kernel is done (stream order)]
-    // + for a statistics-only replay the per-task outputs the fused statistics epilogue reads back
-    const size_t ring_bytes = (size_t)a.R * (size_t)a.N * ((size_t)1 << a.q_log2) * sizeof(fognet::RingWord);
-    const int32_t slots = fallback_slots(a.R, a.T, a.N, ring_bytes, false, a.policy);
-    const size_t fb_bytes = fognet::replay_wide_workspace_bytes(slots, a.T, a.N, false, a.policy);
-    const size_t o_board = align256(256 + (size_t)a.R * sizeof(int32_t));
-    const size_t head = o_board + fognet::kBoardWords * sizeof(uint32_t);
-    const size_t body = ring_bytes > fb_bytes ? ring_bytes : fb_bytes;
-    const size_t RT = stats_only && !a.inloop ? (size_t)a.R * (size_t)a.T : 0;
-    const size_t o_node = head + align256(body), o_st = o_node + align256(RT * 4), o_start = o_st + align256(RT),
-                 o_done = o_start + align256(RT * 8), total = o_done + align256(RT * 8);
-    rc = ensure(c, (void**)&c->ring, &c->ring_bytes, total, "ring workspace");
-    if (rc) return rc;
-    unsigned char* const base = reinterpret_cast<unsigned char*>(c->ring);
-    a.wide_count = reinterpret_cast<int32_t*>(base);
-    a.wide_list = reinterpret_cast<int32_t*>(base + 256);
-    a.ring = reinterpret_cast<fognet::RingWord*>(base + head);
-    if (stats_only && !a.inloop) {
-      a.out_node = reinterpret_cast<int32_t*>(base + o_node);
-      a.out_status = reinterpret_cast<uint8_t*>(base + o_st);
-      a.out_start = reinterpret_cast<int64_t*>(base + o_start);
-      a.out_done = reinterpret_cast<int64_t*>(base + o_done);
-    }
-    e = hipMemsetAsync(a.wide_count, 0, sizeof(int32_t), (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(c, e, "hand-over counter");
-    if (!a.inloop) {  // replay_kernel's progress board: every slot empty
-      a.board = reinterpret_cast<uint32_t*>(base + o_board);
-      e = hipMemsetAsync(a.board, 0xFF, fognet::kBoardWords * sizeof(uint32_t), (hipStream_t)stream);
-      if (e != hipSuccess) return hip_fail(c, e, "progress board");
-    }
-    e = fognet::launch_replay(a, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(c, e, "replay launch");
-    // the handed-over replications (usually none: every workgroup leaves at once).  The wide kernel
-    // accumulates its statistics inline; in a replay-only call the statistics stage that follows
-    // recomputes them for every replication from the per-task outputs, so the hand-over must not add
-    // its histogram and energy as well
-    fognet::ReplayArgs hw = a;
-    if (!a.fuse_stats) {
-      hw.hist = nullptr;
-      hw.out_energy = nullptr;
-    }
-    e = fognet::launch_replay_wide(hw, base + head, slots, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(c, e, "wide hand-over launch");
-  }
-  if (which & 2) {
-    e = fognet::launch_rep_stats(a, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(c, e, "stats launch");
-  }
-  return FOGNET_OK;
-}
-
 int fognet_run_generated_dev(fognet_ctx* c, const fognet_gen_params* p, int64_t r0, const fognet_batch_in* in,
                              fognet_batch_out* out, void* stream) {
   if (!c || !p || !in || !out) return FOGNET_ERR_ARG;
@@ -675,35 +641,28 @@ int fognet_run_generated_dev(fognet_ctx* c, const fognet_gen_params* p, int64_t 
   a.out_energy = out->node_energy_j;
   a.hist = out->hist;
   if (a.out_energy && !a.p_busy) return fail(c, FOGNET_ERR_ARG, "node_energy_j needs the power model (p_busy_w/p_idle_w)");
-  hipError_t e;
-  if (use_wide(a.N) || long_run || a.policy == FOGNET_POLICY_EXT_HIER) {
-    const size_t ws = fognet::replay_wide_workspace_bytes(a.R, a.T, a.N, true, a.policy);
-    rc = ensure(c, (void**)&c->ring, &c->ring_bytes, ws, "wide replay workspace");
-    if (rc) return rc;
-    e = fognet::launch_replay_wide(a, c->ring, a.R, (hipStream_t)stream);
-    return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "wide replay launch");
-  }
-  // workspace: [hand-over counter, work counter | list [R] | rings of the resident workgroups, reused by
-  // the wide hand-over]
+  const hipStream_t s = (hipStream_t)stream;
+  if (use_wide(a.N) || long_run || a.policy == FOGNET_POLICY_EXT_HIER) return run_wide(c, a, s);
+  // the rings of the resident workgroups, reused by the wide hand-over
   const int64_t resident = (int64_t)c->cus * fognet::kGenWavesPerCu;
   a.gen_slots = (int32_t)(a.R < resident ? a.R : resident);
   const size_t ring_bytes = (size_t)a.gen_slots * (size_t)a.N * ((size_t)1 << a.q_log2) * sizeof(fognet::RingWord);
   const int32_t slots = fallback_slots(a.R, a.T, a.N, ring_bytes, true, a.policy);
   const size_t fb_bytes = fognet::replay_wide_workspace_bytes(slots, a.T, a.N, true, a.policy);
-  const size_t head = align256(256 + (size_t)a.R * sizeof(int32_t));
-  rc = ensure(c, (void**)&c->ring, &c->ring_bytes, head + (ring_bytes > fb_bytes ? ring_bytes : fb_bytes),
-              "ring workspace");
+  fognet::ReplayWs w;
+  rc = carve(c, "ring workspace", [&](fognet::WsCursor& v) {
+    return fognet::generated_ws(w, a.R, ring_bytes, fb_bytes, v);
+  });
   if (rc) return rc;
-  unsigned char* const base = reinterpret_cast<unsigned char*>(c->ring);
-  a.wide_count = reinterpret_cast<int32_t*>(base);
-  a.wide_list = reinterpret_cast<int32_t*>(base + 256);
-  a.ring = reinterpret_cast<fognet::RingWord*>(base + head);
-  a.queue = reinterpret_cast<int32_t*>(base + sizeof(int32_t));
-  e = hipMemsetAsync(base, 0, 2 * sizeof(int32_t), (hipStream_t)stream);
+  a.wide_count = w.count;
+  a.wide_list = w.list;
+  a.ring = reinterpret_cast<fognet::RingWord*>(w.body);
+  a.queue = w.count + 1;
+  hipError_t e = hipMemsetAsync(w.count, 0, 2 * sizeof(int32_t), s);
   if (e != hipSuccess) return hip_fail(c, e, "hand-over and work counters");
-  e = fognet::launch_replay(a, (hipStream_t)stream);
+  e = fognet::launch_replay(a, s);
   if (e != hipSuccess) return hip_fail(c, e, "replay launch");
-  e = fognet::launch_replay_wide(a, base + head, slots, (hipStream_t)stream);
+  e = fognet::launch_replay_wide(a, w.body, slots, s);
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "wide hand-over launch");
 }
 
@@ -726,84 +685,70 @@ int fognet_run_batch(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_out*
   if (rc) return rc;
   rc = set_device(c);
   if (rc) return rc;
-  const size_t R = (size_t)in->R, T = (size_t)in->T, N = (size_t)in->N;
-  const size_t NR = in->node_stride ? R : 1;
+  const size_t R = (size_t)in->R, RT = R * (size_t)in->T, N = (size_t)in->N;
+  const size_t NRN = (in->node_stride ? R : 1) * N;
   const size_t HB = FOGNET_HIST_METRICS * FOGNET_HIST_BINS * sizeof(int64_t);
-  const bool pw = in->p_busy_w != nullptr;
-  const bool dn = in->down_tick != nullptr;
-  // inputs 0..8, outputs 9..15, region 16
-  const void* hsrc[9] = {in->arrive_tick, in->req_mips, in->mips, in->dl_tick, in->ul_tick, in->init_adv_tick,
-                         in->p_busy_w, in->p_idle_w, in->down_tick};
-  const size_t isz[9] = {R * T * 8, R * T * 4, NR * N * 4, NR * N * 8, NR * N * 8, NR * N * 8,
-                         pw ? NR * N * 8 : 0, pw ? NR * N * 8 : 0, dn ? NR * N * 8 : 0};
+  // One device buffer per present host array (an absent optional one stays null): src is copied in
+  // before the launch, dst copied out after it; hist is both, because it is added to.
+  struct Buf { const void* src; void* dst; size_t bytes; bool present; void* dev; };
+  enum { kRegion, kArrive, kReq, kMips, kDl, kUl, kInit, kPBusy, kPIdle, kDown,
+         kNode, kStatus, kStart, kDone, kStats, kEnergy, kHist, kBufs };
   const bool rg = in->policy == FOGNET_POLICY_EXT_HIER && in->region != nullptr;
-  void* hdst[7] = {out->node, out->status, out->start_tick, out->done_tick, out->stats, out->node_energy_j,
-                   out->hist};
-  const size_t osz[7] = {R * T * 4, R * T * 1, R * T * 8, R * T * 8, R * sizeof(fognet_rep_stats),
-                         out->node_energy_j ? R * N * 8 : 0, out->hist ? HB : 0};
-  void* d[17] = {};
-  auto cleanup = [&]() {
-    for (int i = 0; i < 17; ++i)
-      if (d[i]) (void)hipFree(d[i]);
+  Buf b[kBufs] = {
+      {in->region, nullptr, RT * 4, rg},
+      {in->arrive_tick, nullptr, RT * 8, true},
+      {in->req_mips, nullptr, RT * 4, true},
+      {in->mips, nullptr, NRN * 4, true},
+      {in->dl_tick, nullptr, NRN * 8, true},
+      {in->ul_tick, nullptr, NRN * 8, true},
+      {in->init_adv_tick, nullptr, NRN * 8, true},
+      {in->p_busy_w, nullptr, NRN * 8, in->p_busy_w != nullptr},
+      {in->p_idle_w, nullptr, NRN * 8, in->p_busy_w != nullptr},
+      {in->down_tick, nullptr, NRN * 8, in->down_tick != nullptr},
+      {nullptr, out->node, RT * 4, out->node != nullptr},  // (statistics only: no per-task outputs)
+      {nullptr, out->status, RT * 1, out->status != nullptr},
+      {nullptr, out->start_tick, RT * 8, out->start_tick != nullptr},
+      {nullptr, out->done_tick, RT * 8, out->done_tick != nullptr},
+      {nullptr, out->stats, R * sizeof(fognet_rep_stats), true},
+      {nullptr, out->node_energy_j, R * N * 8, out->node_energy_j != nullptr},
+      {out->hist, out->hist, HB, out->hist != nullptr},
   };
-  if (rg) {
-    hipError_t e = hipMalloc(&d[16], R * T * 4 ? R * T * 4 : 8);
-    if (e == hipSuccess && R * T) e = hipMemcpyAsync(d[16], in->region, R * T * 4, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) {
-      cleanup();
-      return hip_fail(c, e, "region copy-in");
+  rc = [&]() -> int {
+    hipError_t e;
+    for (Buf& x : b) {
+      if (!x.present) continue;
+      const bool region = &x == &b[kRegion];
+      if ((e = hipMalloc(&x.dev, x.bytes ? x.bytes : 8)) != hipSuccess)
+        return hip_fail(c, e, region ? "region copy-in" : "hipMalloc batch");
+      if (x.src && x.bytes && (e = hipMemcpyAsync(x.dev, x.src, x.bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
+        return hip_fail(c, e, region ? "region copy-in" : "copy-in");
     }
-  }
-  for (int i = 0; i < 16; ++i) {
-    const size_t sz = i < 9 ? isz[i] : osz[i - 9];
-    if (i >= 6 && i < 8 && !pw) continue;
-    if (i == 8 && !dn) continue;
-    if (i >= 9 && i < 13 && !hdst[i - 9]) continue;  // statistics only: no per-task outputs
-    if (i >= 14 && !hdst[i - 9]) continue;
-    hipError_t e = hipMalloc(&d[i], sz ? sz : 8);
-    if (e != hipSuccess) {
-      cleanup();
-      return hip_fail(c, e, "hipMalloc batch");
-    }
-    if (i < 9 && sz) e = hipMemcpyAsync(d[i], hsrc[i], sz, hipMemcpyHostToDevice, c->stream);
-    if (i == 15 && e == hipSuccess) e = hipMemcpyAsync(d[i], hdst[6], sz, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) {
-      cleanup();
-      return hip_fail(c, e, "copy-in");
-    }
-  }
-  fognet_batch_in din = *in;
-  din.arrive_tick = (const int64_t*)d[0];
-  din.req_mips = (const int32_t*)d[1];
-  din.mips = (const int32_t*)d[2];
-  din.dl_tick = (const int64_t*)d[3];
-  din.ul_tick = (const int64_t*)d[4];
-  din.init_adv_tick = (const int64_t*)d[5];
-  din.p_busy_w = (const double*)d[6];
-  din.p_idle_w = (const double*)d[7];
-  din.down_tick = (const int64_t*)d[8];
-  din.region = (const int32_t*)d[16];
-  fognet_batch_out dout = {(int32_t*)d[9], (uint8_t*)d[10], (int64_t*)d[11], (int64_t*)d[12],
-                           (fognet_rep_stats*)d[13], (double*)d[14], (int64_t*)d[15]};
-  rc = fognet_run_batch_dev(c, &din, &dout, c->stream);
-  if (rc) {
-    cleanup();
-    return rc;
-  }
-  for (int i = 0; i < 7; ++i) {
-    if (!hdst[i] || !osz[i]) continue;
-    hipError_t e = hipMemcpyAsync(hdst[i], d[9 + i], osz[i], hipMemcpyDeviceToHost, c->stream);
-    if (e != hipSuccess) {
-      cleanup();
-      return hip_fail(c, e, "copy-out");
-    }
-  }
-  hipError_t e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    cleanup();
-    return hip_fail(c, e, "batch sync");
-  }
-  cleanup();
+    fognet_batch_in din = *in;
+    din.region = (const int32_t*)b[kRegion].dev;
+    din.arrive_tick = (const int64_t*)b[kArrive].dev;
+    din.req_mips = (const int32_t*)b[kReq].dev;
+    din.mips = (const int32_t*)b[kMips].dev;
+    din.dl_tick = (const int64_t*)b[kDl].dev;
+    din.ul_tick = (const int64_t*)b[kUl].dev;
+    din.init_adv_tick = (const int64_t*)b[kInit].dev;
+    din.p_busy_w = (const double*)b[kPBusy].dev;
+    din.p_idle_w = (const double*)b[kPIdle].dev;
+    din.down_tick = (const int64_t*)b[kDown].dev;
+    fognet_batch_out dout = {(int32_t*)b[kNode].dev, (uint8_t*)b[kStatus].dev, (int64_t*)b[kStart].dev,
+                             (int64_t*)b[kDone].dev, (fognet_rep_stats*)b[kStats].dev, (double*)b[kEnergy].dev,
+                             (int64_t*)b[kHist].dev};
+    const int rc_run = fognet_run_batch_dev(c, &din, &dout, c->stream);
+    if (rc_run) return rc_run;
+    for (Buf& x : b)
+      if (x.dev && x.dst && x.bytes &&
+          (e = hipMemcpyAsync(x.dst, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
+        return hip_fail(c, e, "copy-out");
+    e = hipStreamSynchronize(c->stream);
+    return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "batch sync");
+  }();
+  for (Buf& x : b)  // on every exit
+    if (x.dev) (void)hipFree(x.dev);
+  if (rc) return rc;
   if (out->stats)
     for (size_t r = 0; r < R; ++r)
       if (out->stats[r].status != FOGNET_OK) {

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "fognet_hip.h"
+#include "workspace.h"
 
 namespace fognet {
 
@@ -282,7 +283,6 @@ struct ReplayArgs {
   // FOGNET_FLAG_REF_ABORT: a replication with an abort point gets status FOGNET_REF_ABORTED
   int32_t ref_abort;
 };
-constexpr size_t kBoardWords = (size_t)1 << 17;  // 8 XCC x 8 SE x 2 SH x 16 CU x 4 SIMD x 16 slots
 
 // Generated-mode launch: 3 waves per SIMD, 4 SIMDs per CU (replay_gen_kernel)
 constexpr int kGenWavesPerCu = 12;
@@ -313,7 +313,7 @@ struct WideEntry {
   int32_t next;  // next task on the same node (valid while this one is pending)
   int32_t pad;   // 1: escalated to the parent broker (FOGNET_POLICY_EXT_HIER)
 };
-static_assert(sizeof(WideEntry) == 40, "wide entry is 40 B");
+static_assert(sizeof(WideEntry) == kWideEntryBytes, "wide entry is 40 B (workspace.h)");
 
 // Per node: chain ends plus copies of the head's and tail's fields, so a push
 // or an advert starts from one 64-B record (one cache line) instead of
@@ -330,7 +330,7 @@ struct WideNode {
   uint64_t tl_C;    //       cumulative service (0: no task yet) = the node's service seconds so far
   uint32_t hd_S, tl_S;  // (bit 31 of tl_S: the tail was escalated, FOGNET_POLICY_EXT_HIER)
 };
-static_assert(sizeof(WideNode) == 64, "wide node record is one 64-B line");
+static_assert(sizeof(WideNode) == kWideNodeBytes, "wide node record is one 64-B line (workspace.h)");
 
 // LDS of the wide kernel: per lane and group of 16 of its nodes the earliest
 // advert, its node, the smallest view key and run-horizon bound (28 B) + the histogram; the
@@ -341,8 +341,7 @@ constexpr int kWideMaxNodes = 65536;  // LDS: 115 KiB of group minima (FOGNET_PO
 // 1,024 nodes per workspace slot), up to:
 constexpr int kWideBigMaxNodes = 1 << 20;
 size_t replay_wide_lds_bytes(int32_t N);
-// workspace: R*T WideEntry followed by R*N WideNode
-// (+ R*N generated node parameters in generated mode, + the HBM group minima above kWideMaxNodes)
+// workspace: wide_ws (replay_wide.hip) is its layout
 size_t replay_wide_workspace_bytes(int32_t R, int32_t T, int32_t N, bool gen, int policy);
 // FOGNET_POLICY_EXT_HIER by region (replay_region.hip): one wavefront per
 // (replication, region) over the region's publishes while no escalation occurs;
@@ -351,6 +350,7 @@ size_t replay_wide_workspace_bytes(int32_t R, int32_t T, int32_t N, bool gen, in
 struct RegionRec {
   int32_t n_done, max_pend, status, pad;
 };
+static_assert(sizeof(RegionRec) == kRegionRecBytes, "region record is 16 B (workspace.h)");
 struct RegionWs {
   WideEntry* e;    // [R][T] chain entries, indexed by the task's position in the region-sorted order
   WideNode* nd;    // [R][N]
@@ -385,7 +385,6 @@ struct RegionWs {
 // sort + order + the first region pass; resume: + the second pass over the escalated replications;
 // then the finish kernel (statistics, hand-over list)
 hipError_t launch_replay_region(const ReplayArgs& a, const RegionWs& w, bool resume, hipStream_t s);
-constexpr size_t kRegionResumeBytes = 192;  // >= sizeof(Acc) + sizeof(AbortPt) (replay_common.h)
 
 // slots: workspace slots (workgroups).  With a.wide_list unset, slots == R and
 // workgroup r replays replication r; with it set, the workgroups take the

@@ -1691,9 +1691,24 @@ static size_t v2_rows(int32_t N) {
   return npl * kWave;
 }
 
-size_t replay_v2_workspace_bytes(int32_t R, int32_t T, int32_t N, int32_t q_log2) {
+// Workspace layout (launch_replay_v2, replay_v2_workspace_bytes), packed:
+// [inq, q V2Msg | outq, q V2Msg | res, q V2Res | list, R*T bytes], q = the queue rows of all replications << q_log2
+struct V2Ws {
+  size_t outq_off, res_off, list_off, bytes;
+};
+
+static V2Ws v2_ws(int32_t R, int32_t T, int32_t N, int32_t q_log2) {
   const size_t q = (size_t)R * v2_rows(N) << q_log2;
-  return q * (2 * sizeof(V2Msg) + sizeof(V2Res)) + (size_t)R * (size_t)T;
+  V2Ws w;
+  w.outq_off = q * sizeof(V2Msg);
+  w.res_off = w.outq_off + q * sizeof(V2Msg);
+  w.list_off = w.res_off + q * sizeof(V2Res);
+  w.bytes = w.list_off + (size_t)R * (size_t)T;
+  return w;
+}
+
+size_t replay_v2_workspace_bytes(int32_t R, int32_t T, int32_t N, int32_t q_log2) {
+  return v2_ws(R, T, N, q_log2).bytes;
 }
 
 hipError_t launch_replay_v2(const fognet_v2_in& in, const fognet_v2_out& out, void* ws, int32_t q_log2,
@@ -1703,11 +1718,12 @@ hipError_t launch_replay_v2(const fognet_v2_in& in, const fognet_v2_out& out, vo
   a.in = in;
   a.out = out;
   a.q_log2 = q_log2;
-  const size_t q = (size_t)in.R * v2_rows(in.N) << q_log2;
-  a.inq = reinterpret_cast<V2Msg*>(ws);
-  a.outq = a.inq + q;
-  a.res = reinterpret_cast<V2Res*>(a.outq + q);
-  a.list = reinterpret_cast<uint8_t*>(a.res + q);
+  const V2Ws w = v2_ws(in.R, in.T, in.N, q_log2);
+  unsigned char* const base = static_cast<unsigned char*>(ws);
+  a.inq = reinterpret_cast<V2Msg*>(base);
+  a.outq = reinterpret_cast<V2Msg*>(base + w.outq_off);
+  a.res = reinterpret_cast<V2Res*>(base + w.res_off);
+  a.list = base + w.list_off;
   // rows of 16 lanes unless FOGNET_V2_ROW=32 (two replications per wavefront) or N > 16
   const char* rw = getenv("FOGNET_V2_ROW");
   const int row = (in.N > 16 || (rw && strcmp(rw, "32") == 0)) ? 32 : 16;

@@ -31,7 +31,7 @@ pytestmark = pytest.mark.gpu
 GEN_WAVES_PER_CU = 12      # kGenWavesPerCu, csrc/internal.h:288
 WIDE_FALLBACK_SLOTS = 1024  # kWideFallbackSlots, csrc/capi.hip:56 (fallback_slots() only lowers it)
 DEFAULT_RING = 2048        # kDefaultRing, csrc/capi.hip:53
-REDUCE_CHUNK = 4096        # kReduceChunk, csrc/internal.h:403
+REDUCE_CHUNK = 4096        # kReduceChunk, csrc/internal.h:402
 NODE_KEYS = ("arrive", "req", "mips", "dl", "ul", "init")
 
 
@@ -95,7 +95,7 @@ def generated_job_against_oracle(ctx, N, policy, r0, ring):
 
 
 def assert_past_one_resident_round(ctx):
-    # generated mode launches min(R, CUs * kGenWavesPerCu) workgroups (capi.hip:688-689,
+    # generated mode launches min(R, CUs * kGenWavesPerCu) workgroups (capi.hip, fognet_run_generated_dev;
     # replay.hip:1377); three rounds' worth: most workgroups replay a third replication
     cus = torch.cuda.get_device_properties(torch.device("cuda", ctx.device)).multi_processor_count
     assert GEN_R >= 3 * GEN_WAVES_PER_CU * cus, (GEN_R, cus)
@@ -209,7 +209,7 @@ def hier_many():
 def test_hier_more_escalating_replications_than_slots(ctx, monkeypatch, hier_many, regions, resume):
     """EXT_HIER with 1,088 of 1,280 replications escalating (oracle census; first
     escalations at publishes 73 .. 399, every residue mod 64): the sequential
-    continuation has min(R, 1,024) slots (capi.hip:528), so 64 slots continue a
+    continuation has min(R, 1,024) slots (capi.hip, run_regions), so 64 slots continue a
     second escalated replication, importing its region state from the resume
     records (resume), or replay it from the start (FOGNET_HIER_RESUME=0); 192
     replications are finished by the region pass.  FOGNET_HIER_REGIONS=0: the
