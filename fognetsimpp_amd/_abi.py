@@ -111,6 +111,16 @@ USER_STATS_DTYPE = np.dtype([(n, MOMENTS_DTYPE) for n in USER_SIGNALS])
 assert USER_STATS_DTYPE.itemsize == C.sizeof(UserStats)
 
 
+class NodeStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_tasks", "n_queued", "n_started", "n_lost", "busy_s", "last_tick")] + \
+               [("queue", Moments), ("resp", Moments)]
+
+
+NODE_STATS_DTYPE = np.dtype([(n, np.int64) for n in ("n_tasks", "n_queued", "n_started", "n_lost", "busy_s",
+                                                      "last_tick")] + [("queue", MOMENTS_DTYPE), ("resp", MOMENTS_DTYPE)])
+assert NODE_STATS_DTYPE.itemsize == C.sizeof(NodeStats)
+
+
 class BatchIn(C.Structure):
     _fields_ = [
         ("R", C.c_int32), ("T", C.c_int32), ("N", C.c_int32), ("policy", C.c_int32),
@@ -193,6 +203,10 @@ SIGNATURES = {
     "fognet_user_stats_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P, P, C.c_int32, P, P]),
     "fognet_run_v2_dev": (C.c_int, [P, C.POINTER(V2In), C.POINTER(V2Out), P]),
     "fognet_reduce_stats_dev": (C.c_int, [P, P, C.c_int32, P, P]),
+    "fognet_node_stats_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P, P]),
+    "fognet_reduce_node_stats_dev": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, P]),
+    "fognet_node_stats_init": (None, [C.POINTER(NodeStats)]),
+    "fognet_node_stats_merge": (None, [C.POINTER(NodeStats), C.POINTER(NodeStats)]),
     "fognet_job_stats_init": (None, [C.POINTER(JobStats)]),
     "fognet_job_stats_merge": (None, [C.POINTER(JobStats), C.POINTER(JobStats)]),
     "fognet_job_stats_add_rep": (None, [C.POINTER(JobStats), C.POINTER(RepStats)]),
@@ -212,6 +226,7 @@ SIGNATURES = {
     "fognet_trace_info_read": (C.c_int, [C.c_char_p, C.POINTER(TraceInfo)]),
     "fognet_trace_read": (C.c_int, [C.c_char_p, C.POINTER(BatchIn), P]),
     "fognet_write_sca": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(JobStats), P]),
+    "fognet_write_sca_nodes": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int]),
     "fognet_write_vec": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P, P, P, P, P, P]),
     "fognet_gen_trace_mqtt": (C.c_int, [C.c_uint32, C.c_int32, P, P, P, P, C.c_int64, C.c_int32, C.c_int32,
                                         C.c_int32, P, P, P, C.POINTER(C.c_int32)]),

@@ -779,6 +779,46 @@ int fognet_user_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "user stats launch");
 }
 
+int fognet_node_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out,
+                          fognet_node_stats* node_stats, void* stream) {
+  if (!c || !out) return FOGNET_ERR_ARG;
+  if (in && in->policy == FOGNET_POLICY_EXT_HIER)
+    return fail(c, FOGNET_ERR_UNSUPPORTED,
+                "node statistics under EXT_HIER: an escalated task reaches its node hier_up_tick later, and the "
+                "per-task outputs do not say which tasks were escalated");
+  fognet::ReplayArgs a;
+  int rc = prepare(c, in, &a);
+  if (rc) return rc;
+  if (a.R == 0) return FOGNET_OK;
+  if (!out->stats) return fail(c, FOGNET_ERR_ARG, "null stats");
+  if (a.T > 0 && (!out->node || !out->status || !out->start_tick || !out->done_tick))
+    return fail(c, FOGNET_ERR_ARG, "node statistics need the per-task outputs (a statistics-only out has none)");
+  if (!node_stats) return fail(c, FOGNET_ERR_ARG, "null node_stats");
+  rc = set_device(c);
+  if (rc) return rc;
+  a.out_node = out->node;
+  a.out_status = out->status;
+  a.out_start = out->start_tick;
+  a.out_done = out->done_tick;
+  a.out_stats = out->stats;
+  // FOGNET_NODE_STATS=hbm: the accumulators are the caller's records for every N (the layout of
+  // N > node_stats_lds_max()), so small tests run both layouts on the same traces
+  const hipError_t e = fognet::launch_node_stats(a, node_stats, env_is("FOGNET_NODE_STATS", "hbm"), (hipStream_t)stream);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "node stats launch");
+}
+
+int fognet_reduce_node_stats_dev(fognet_ctx* c, const fognet_node_stats* node_stats, const fognet_rep_stats* stats,
+                                 int32_t R, int32_t N, fognet_node_stats* out, void* stream) {
+  if (!c) return FOGNET_ERR_ARG;
+  if (R < 0 || N < 0) return fail(c, FOGNET_ERR_ARG, "negative R/N");
+  if (N == 0) return FOGNET_OK;
+  if (!out || (R > 0 && (!node_stats || !stats))) return fail(c, FOGNET_ERR_ARG, "null pointer");
+  const int rc = set_device(c);
+  if (rc) return rc;
+  const hipError_t e = fognet::launch_reduce_node_stats(node_stats, stats, R, N, out, (hipStream_t)stream);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "node reduce launch");
+}
+
 int fognet_run_v2_dev(fognet_ctx* c, const fognet_v2_in* in, fognet_v2_out* out, void* stream) {
   if (!c || !in || !out) return FOGNET_ERR_ARG;
   if (in->R < 0 || in->T < 0 || in->N < 0) return fail(c, FOGNET_ERR_ARG, "negative R/T/N");
@@ -895,6 +935,48 @@ void fognet_job_stats_add_rep(fognet_job_stats* a, const fognet_rep_stats* s) {
   b.resp_sq[0] = s->resp_sq_lo;
   b.resp_sq[1] = s->resp_sq_hi;
   fognet_job_stats_merge(a, &b);
+}
+
+static void moments_init_host(fognet_moments* m) {
+  memset(m, 0, sizeof *m);
+  m->min_raw = INT64_MAX;
+  m->max_raw = INT64_MIN;
+}
+
+static void moments_merge_host(fognet_moments* a, const fognet_moments* b) {
+  a->count += b->count;
+  a->overflow += b->overflow;
+  if (b->min_raw < a->min_raw) a->min_raw = b->min_raw;
+  if (b->max_raw > a->max_raw) a->max_raw = b->max_raw;
+  const unsigned __int128 s = (unsigned __int128)a->sum_lo + b->sum_lo;  // two's complement, modulo 2^128
+  a->sum_lo = (uint64_t)s;
+  a->sum_hi = a->sum_hi + b->sum_hi + (uint64_t)(s >> 64);
+  uint64_t q[3] = {a->sq_lo, a->sq_hi, a->sq_top};
+  const uint64_t bq[3] = {b->sq_lo, b->sq_hi, b->sq_top};
+  add192_host(q, bq);
+  a->sq_lo = q[0];
+  a->sq_hi = q[1];
+  a->sq_top = q[2];
+}
+
+void fognet_node_stats_init(fognet_node_stats* s) {
+  if (!s) return;
+  memset(s, 0, sizeof *s);
+  s->last_tick = INT64_MIN;
+  moments_init_host(&s->queue);
+  moments_init_host(&s->resp);
+}
+
+void fognet_node_stats_merge(fognet_node_stats* a, const fognet_node_stats* b) {
+  if (!a || !b) return;
+  a->n_tasks += b->n_tasks;
+  a->n_queued += b->n_queued;
+  a->n_started += b->n_started;
+  a->n_lost += b->n_lost;
+  a->busy_s += b->busy_s;
+  if (b->last_tick > a->last_tick) a->last_tick = b->last_tick;
+  moments_merge_host(&a->queue, &b->queue);
+  moments_merge_host(&a->resp, &b->resp);
 }
 
 int fognet_gen_trace_dev(fognet_ctx* c, const fognet_gen_params* p, int64_t r0, int32_t R, int32_t T, int32_t N,

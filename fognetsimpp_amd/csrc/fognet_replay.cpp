@@ -37,6 +37,7 @@
 #include <string>
 #include <chrono>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "fognet_hip.h"
@@ -333,7 +334,7 @@ struct Options {
   int nodes = 0, reps = 1, device = 0, ring = 0;
   uint32_t seed = 1;
   int64_t dl = kMs, ul = kMs, user_ul = kMs, user_dl = kMs, stop = kNoTick;
-  bool user_dl_set = false, dry_run = false, policy_set = false, quiet = false, show = false;
+  bool user_dl_set = false, dry_run = false, policy_set = false, quiet = false, show = false, node_stats = false;
   int policy = FOGNET_POLICY_REF_V3;
   double p_busy = -1.0, p_idle = -1.0;
 };
@@ -471,6 +472,7 @@ void usage() {
       "  --power BUSY,IDLE    node power model in W (builder-defined energy statistic)\n"
       "  --ring N             per-node pending capacity (power of two)\n"
       "  --trace-out FILE     write the FOGNTRC1 trace  --sca FILE / --vec FILE (replication 0)\n"
+      "  --node-stats         with --sca: append one block per fog node (tasks, queueTime, response)\n"
       "  --device D           HIP device (default 0)\n"
       "  --world W --rank K --comm-id FILE   one process per GPU: rank K replays its block of the\n"
       "                       --reps replications; the job statistics are exchanged over RCCL\n"
@@ -524,6 +526,7 @@ Options parse_args(int argc, char** argv) {
     } else if (a == "--dry-run") o.dry_run = true;
     else if (a == "--quiet") o.quiet = true;
     else if (a == "--show") o.show = true;
+    else if (a == "--node-stats") o.node_stats = true;
     else if (a == "--world") o.world = (int)parse_int(need(i), "--world");
     else if (a == "--rank") o.rank = (int)parse_int(need(i), "--rank");
     else if (a == "--comm-id") o.comm_id = need(i);
@@ -535,6 +538,7 @@ Options parse_args(int argc, char** argv) {
   if (o.ini.empty() == o.trace_in.empty()) die("give exactly one of -f INI and --trace FILE (--help)");
   if (o.reps <= 0) die("--reps must be > 0");
   if (o.world < 1 || o.rank < 0 || o.rank >= o.world) die("--world / --rank: need 0 <= rank < world");
+  if (o.node_stats && o.world > 1) die("--node-stats: the per-node records of several ranks are not combined (--world 1)");
   if (o.world > 1 && o.comm_id.empty()) die("--world > 1 needs --comm-id FILE (the communicator id's rendezvous)");
   if (o.reps < o.world) die("--reps must be >= --world (every rank replays a block of replications)");
   if (o.ring != 0 && (o.ring < 2 || o.ring > (1 << 15) || (o.ring & (o.ring - 1)) != 0))
@@ -624,6 +628,50 @@ void exchange_stats(const Options& o, fognet_ctx* ctx, fognet_job_stats* job, st
   fognet_comm_destroy(comm);
 }
 
+template <class T>
+T* dev_copy(const std::vector<T>& h) {
+  void* p = nullptr;
+  hip_check(hipMalloc(&p, std::max<size_t>(1, h.size() * sizeof(T))), "hipMalloc");
+  if (!h.empty()) hip_check(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
+  return static_cast<T*>(p);
+}
+
+template <class T>
+T* dev_alloc(size_t n) {
+  void* p = nullptr;
+  hip_check(hipMalloc(&p, std::max<size_t>(1, n * sizeof(T))), "hipMalloc");
+  return static_cast<T*>(p);
+}
+
+// --node-stats: the per-node records of the finished replay (fognet_node_stats_dev over device copies of
+// the trace and the per-task outputs), reduced over the replications (fognet_reduce_node_stats_dev) and
+// appended to the job's .sca, one block per fog node module.
+void append_node_stats(const Options& o, fognet_ctx* ctx, const fognet_batch_in& in, const fognet_batch_out& out,
+                       const std::string& network, const std::string& run_id) {
+  const size_t R = (size_t)in.R, RT = R * (size_t)in.T, N = (size_t)in.N, NRN = (in.node_stride ? R : 1) * N;
+  auto up = [](const auto* h, size_t n) {
+    return dev_copy(std::vector<std::remove_cv_t<std::remove_pointer_t<decltype(h)>>>(h, h + n));
+  };
+  fognet_batch_in din = in;
+  din.arrive_tick = up(in.arrive_tick, RT), din.req_mips = up(in.req_mips, RT), din.mips = up(in.mips, NRN);
+  din.dl_tick = up(in.dl_tick, NRN), din.ul_tick = up(in.ul_tick, NRN), din.init_adv_tick = up(in.init_adv_tick, NRN);
+  din.p_busy_w = din.p_idle_w = nullptr;
+  din.down_tick = nullptr;
+  fognet_batch_out dout{up(out.node, RT), up(out.status, RT), up(out.start_tick, RT), up(out.done_tick, RT),
+                        up(out.stats, R), nullptr, nullptr};
+  fognet_node_stats* d_nodes = dev_alloc<fognet_node_stats>(R * N);
+  fognet_node_stats* d_job = dev_alloc<fognet_node_stats>(N);
+  check_ctx(ctx, fognet_node_stats_dev(ctx, &din, &dout, d_nodes, nullptr), "fognet_node_stats_dev");
+  check_ctx(ctx, fognet_reduce_node_stats_dev(ctx, d_nodes, dout.stats, in.R, in.N, d_job, nullptr),
+            "fognet_reduce_node_stats_dev");
+  std::vector<fognet_node_stats> nodes(N);
+  hip_check(hipMemcpy(nodes.data(), d_job, N * sizeof(fognet_node_stats), hipMemcpyDeviceToHost), "hipMemcpy");
+  const void* bufs[] = {din.arrive_tick, din.req_mips, din.mips, din.dl_tick, din.ul_tick, din.init_adv_tick,
+                        dout.node, dout.status, dout.start_tick, dout.done_tick, dout.stats, d_nodes, d_job};
+  for (const void* b : bufs) (void)hipFree(const_cast<void*>(b));
+  check(fognet_write_sca_nodes(o.sca.c_str(), run_id.c_str(), network.c_str(), in.N, nodes.data(), nullptr, 1), "sca nodes");
+}
+
 int run_v3(const Options& o, fognet_batch_in in, const std::string& network, const std::string& run_id) {
   const size_t RT = (size_t)in.R * (size_t)in.T;
   std::vector<int32_t> node(RT);
@@ -664,6 +712,7 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
     return local_failed ? 1 : 0;
   }
   if (!o.sca.empty()) check(fognet_write_sca(o.sca.c_str(), run_id.c_str(), network.c_str(), &job, hist.data()), "sca");
+  if (!o.sca.empty() && o.node_stats) append_node_stats(o, ctx, in, out, network, run_id);
   if (!o.vec.empty()) {  // replication 0's vectors (a failed replication has no complete outputs)
     if (stats[0].status != FOGNET_OK)
       die(std::string("--vec: replication 0 failed: ") + fognet_status_string(stats[0].status));
@@ -691,21 +740,6 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
   }
   fognet_destroy(ctx);
   return job.n_failed ? 1 : 0;
-}
-
-template <class T>
-T* dev_copy(const std::vector<T>& h) {
-  void* p = nullptr;
-  hip_check(hipMalloc(&p, std::max<size_t>(1, h.size() * sizeof(T))), "hipMalloc");
-  if (!h.empty()) hip_check(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
-  return static_cast<T*>(p);
-}
-
-template <class T>
-T* dev_alloc(size_t n) {
-  void* p = nullptr;
-  hip_check(hipMalloc(&p, std::max<size_t>(1, n * sizeof(T))), "hipMalloc");
-  return static_cast<T*>(p);
 }
 
 // BrokerBaseApp2 + ComputeBrokerApp2 (the v2 model replay; device entry point).

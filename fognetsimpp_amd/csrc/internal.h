@@ -416,6 +416,13 @@ hipError_t launch_decide_v2(int64_t m, int32_t n, const int32_t* mips, const int
                             int32_t* node, int32_t* action, hipStream_t s);
 hipError_t launch_user_stats(const ReplayArgs& a, const int64_t* user_ul, const int64_t* user_dl, int32_t per_task,
                              fognet_user_stats* out, hipStream_t s);
+// Per-node statistics of a finished replay and their job reduction (node_stats.hip).  Up to
+// node_stats_lds_max() nodes the accumulators live in LDS unless force_hbm; the reduction is one
+// workgroup per node over any R and needs no workspace.
+int32_t node_stats_lds_max();
+hipError_t launch_node_stats(const ReplayArgs& a, fognet_node_stats* out, bool force_hbm, hipStream_t s);
+hipError_t launch_reduce_node_stats(const fognet_node_stats* in, const fognet_rep_stats* stats, int32_t R, int32_t N,
+                                    fognet_node_stats* out, hipStream_t s);
 // v2 model replay (replay_v2.hip)
 size_t replay_v2_workspace_bytes(int32_t R, int32_t T, int32_t N, int32_t q_log2);
 hipError_t launch_replay_v2(const fognet_v2_in& in, const fognet_v2_out& out, void* workspace, int32_t q_log2,

@@ -473,6 +473,35 @@ int fognet_write_sca(const char* path, const char* run_id, const char* network, 
   return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_sca: write failed: ") + path);
 }
 
+int fognet_write_sca_nodes(const char* path, const char* run_id, const char* network, int32_t N,
+                           const fognet_node_stats* nodes, const int32_t* node_id, int append) {
+  if (!path || !run_id || !network || N < 0 || (N > 0 && !nodes))
+    return fail(FOGNET_ERR_ARG, "write_sca_nodes: bad argument");
+  FILE* f = fopen(path, append ? "a" : "w");
+  if (!f) return fail(FOGNET_ERR_ARG, std::string("write_sca_nodes: cannot open ") + path);
+  if (!append) run_header(f, run_id, network);
+  for (int32_t j = 0; j < N; ++j) {
+    const fognet_node_stats& s = nodes[j];
+    const std::string mod = std::string(network) + ".fogNode[" + std::to_string(node_id ? node_id[j] : j) + "].udpApp[0]";
+    fprintf(f, "scalar %s \ttasks \t%lld\n", mod.c_str(), (long long)s.n_tasks);
+    fprintf(f, "scalar %s \t\"tasks queued\" \t%lld\n", mod.c_str(), (long long)s.n_queued);
+    fprintf(f, "scalar %s \t\"tasks started\" \t%lld\n", mod.c_str(), (long long)s.n_started);
+    fprintf(f, "scalar %s \t\"tasks lost\" \t%lld\n", mod.c_str(), (long long)s.n_lost);
+    fprintf(f, "scalar %s \t\"busy seconds\" \t%lld\n", mod.c_str(), (long long)s.busy_s);
+    // the 128-bit two's complement sums, sign-extended to the 192 bits moments() takes
+    const uint64_t qs[3] = {s.queue.sum_lo, s.queue.sum_hi, (int64_t)s.queue.sum_hi < 0 ? ~(uint64_t)0 : 0};
+    const uint64_t qq[3] = {s.queue.sq_lo, s.queue.sq_hi, s.queue.sq_top};
+    const uint64_t rs[3] = {s.resp.sum_lo, s.resp.sum_hi, 0};
+    const uint64_t rq[3] = {s.resp.sq_lo, s.resp.sq_hi, s.resp.sq_top};
+    statistic(f, mod, "queueTime", "stats", moments(s.queue.count, qs, qq, s.queue.min_raw, s.queue.max_raw, true, true));
+    stat_attrs(f, "queueTime", "stats");
+    statistic(f, mod, "response", "stats", moments(s.resp.count, rs, rq, s.resp.min_raw, s.resp.max_raw, false, false));
+    stat_attrs(f, "response", "stats");
+  }
+  const bool ok = ferror(f) == 0;
+  return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_sca_nodes: write failed: ") + path);
+}
+
 int fognet_write_vec(const char* path, const char* run_id, const char* network, int32_t T, int32_t N,
                      const int64_t* arrive_tick, const int64_t* dl_tick, const int32_t* node, const uint8_t* status,
                      const int64_t* start_tick, const int32_t* node_id) {

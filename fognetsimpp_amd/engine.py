@@ -394,6 +394,71 @@ def user_stats(ctx: Context, trace: dict, out: BatchResult, user_ul, user_dl,
     return res[:nres].cpu().numpy().view(_abi.USER_STATS_DTYPE)
 
 
+def node_stats(ctx: Context, trace: dict, out: BatchResult, policy: str | int = "REF_V3",
+               res: torch.Tensor | None = None) -> torch.Tensor:
+    """Per-node statistics (fognet_node_stats_dev) of a finished replay on the
+    current stream: what the reference records per ComputeBroker module.
+    Returns the device buffer of the records, uint8 [R, N * sizeof(fognet_node_stats)]
+    (``.cpu().numpy().view(_abi.NODE_STATS_DTYPE)`` gives [R, N] records); ``res``:
+    write into this buffer instead of a new one.  ``policy``: the replay's
+    ("REF_V3" or "EXT_LAT"; EXT_HIER is refused, FOGNET_ERR_UNSUPPORTED)."""
+    arrive = trace["arrive"]
+    R, T = arrive.shape
+    dev = arrive.device
+    mips = trace["mips"]
+    N = mips.shape[-1]
+    nres = R * N * _abi.NODE_STATS_DTYPE.itemsize
+    if res is None:
+        res = torch.empty(nres, dtype=torch.uint8, device=dev)
+    else:
+        _check_bytes(res, nres, dev, "res")
+    pol = POLICIES[policy] if isinstance(policy, str) else int(policy)
+    hier = pol == _abi.FOGNET_POLICY_EXT_HIER
+    bi = _abi.BatchIn(R, T, N, pol, N if mips.dim() == 2 else 0, 0,
+                      _ptr(arrive), _ptr(trace["req"]), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
+                      _ptr(trace["init"]), None, None, _ptr(trace.get("down")), _ptr(trace.get("region")) if hier else None)
+    bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick),
+                       _ptr(out.stats), None, None)
+    ctx.check(ctx._lib.fognet_node_stats_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(res), _stream_ptr(dev)),
+              "node_stats")
+    return res[:nres].view(R, N * _abi.NODE_STATS_DTYPE.itemsize)
+
+
+def reduce_node_stats(ctx: Context, node_stats: torch.Tensor, stats: torch.Tensor, R: int, N: int,
+                      out: torch.Tensor | None = None) -> np.ndarray:
+    """Exact job reduction of per-node records on the device
+    (fognet_reduce_node_stats_dev): record j merges node j over the replications
+    whose status is OK.  ``node_stats``: :func:`node_stats`'s buffer; ``stats``:
+    the replications' records (BatchResult.stats).  Returns NODE_STATS_DTYPE [N];
+    ``out``: the device buffer written to (uint8, N * sizeof(fognet_node_stats))."""
+    nout = N * _abi.NODE_STATS_DTYPE.itemsize
+    dev = stats.device
+    if out is None:
+        out = torch.empty(max(nout, 1), dtype=torch.uint8, device=dev)
+    else:
+        _check_bytes(out, nout, dev, "out")
+    if node_stats.numel() < R * nout or stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "node_stats / stats smaller than R replications")
+    ctx.check(ctx._lib.fognet_reduce_node_stats_dev(ctx.handle, _ptr(node_stats), _ptr(stats), R, N, _ptr(out),
+                                                    _stream_ptr(dev)), "reduce_node_stats")
+    return out[:nout].cpu().numpy().view(_abi.NODE_STATS_DTYPE)
+
+
+def merge_node_stats(records) -> np.ndarray:
+    """Exact host merge of per-node record arrays [N] (e.g. one per GPU after an
+    all-gather; fognet_node_stats_merge) into one [N]."""
+    lib = _abi.load()
+    records = [np.ascontiguousarray(r, dtype=_abi.NODE_STATS_DTYPE).reshape(-1) for r in records]
+    N = records[0].size if records else 0
+    acc = (_abi.NodeStats * N)()
+    for j in range(N):
+        lib.fognet_node_stats_init(C.byref(acc[j]))
+        for rec in records:
+            b = _abi.NodeStats.from_buffer_copy(rec[j].tobytes())
+            lib.fognet_node_stats_merge(C.byref(acc[j]), C.byref(b))
+    return np.frombuffer(bytes(acc), dtype=_abi.NODE_STATS_DTYPE).copy()
+
+
 @dataclass
 class V2Result:
     node: torch.Tensor        # [R, T] int32 (-1: served by the broker / no node)
@@ -477,6 +542,17 @@ def summarize_moments(m, raw_ms: bool = True) -> dict:
     d = _fields(n, s, q, m["min_raw"], m["max_raw"], 1e-12 if raw_ms else 1e-9)
     d["overflow"] = int(m["overflow"])
     return d
+
+
+def summarize_node(rec) -> dict:
+    """`.sca`-style view of one per-node record (NODE_STATS_DTYPE): the counts and
+    the node's queueTime (raw values * 1e-12 ms) and response (ticks / 1e9 ms) fields."""
+    resp = summarize_moments(rec["resp"], raw_ms=False)
+    resp.pop("overflow")
+    return {"tasks": int(rec["n_tasks"]), "queued": int(rec["n_queued"]), "started": int(rec["n_started"]),
+            "lost": int(rec["n_lost"]), "busy_s": int(rec["busy_s"]),
+            "last_tick": int(rec["last_tick"]) if int(rec["resp"]["count"]) else None,
+            "queueTime_ms": summarize_moments(rec["queue"]), "response_ms": resp}
 
 
 def reduce_stats(ctx: Context, stats: torch.Tensor, R: int, out: torch.Tensor | None = None) -> np.ndarray:

@@ -98,6 +98,19 @@ def write_sca(path: str, job, hist=None, run_id: str = "General-0-fognet", netwo
            "write_sca")
 
 
+def write_sca_nodes(path: str, nodes, node_id=None, append: bool = False, run_id: str = "General-0-fognet",
+                    network: str = "FogNet") -> None:
+    """Per-node `.sca` blocks of NODE_STATS_DTYPE records [N] (fognet_write_sca_nodes):
+    one module <network>.fogNode[<node_id or index>].udpApp[0] each.  ``append``: add
+    them to the file :func:`write_sca` wrote instead of starting a new one."""
+    rec = np.ascontiguousarray(nodes, dtype=_abi.NODE_STATS_DTYPE).reshape(-1)
+    nid = np.ascontiguousarray(node_id, dtype=np.int32).reshape(-1) if node_id is not None else None
+    if nid is not None and nid.size != rec.size:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "write_sca_nodes: node_id length differs from the records'")
+    _check(_abi.load().fognet_write_sca_nodes(path.encode(), run_id.encode(), network.encode(), rec.size, _p(rec),
+                                              _p(nid), 1 if append else 0), "write_sca_nodes")
+
+
 def write_vec(path: str, arrive, dl, node, status, start, node_id=None, run_id: str = "General-0-fognet",
               network: str = "FogNet") -> None:
     """OMNeT++ .vec of ONE replication: arrive/node/status/start [T], dl [N]."""

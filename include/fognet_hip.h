@@ -299,7 +299,10 @@ typedef struct fognet_batch_out {
  *     (fognet_replay_dev alone writes only the four fields named at its declaration;
  *     fognet_rep_stats_dev completes the record.)  Likewise fognet_v2_stats (every count 0
  *     for a replication refused before its first event) and fognet_user_stats (the
- *     count == 0 values of fognet_moments for a replication with n_tasks = 0). */
+ *     count == 0 values of fognet_moments for a replication with n_tasks = 0).
+ *   The per-node records (fognet_node_stats_dev's [R][N], fognet_reduce_node_stats_dev's [N])
+ *     obey every sentence above: 8-B alignment, nothing outside [R][N] / [N] touched, no
+ *     initialisation needed; a failed replication's row is N empty records. */
 
 /* count / min / max / exact signed 128-bit sum and 192-bit sum of squares of a
  * signal's raw emitted values (min_raw = INT64_MAX, max_raw = INT64_MIN when
@@ -327,6 +330,28 @@ typedef struct fognet_moments {
 typedef struct fognet_user_stats {
     fognet_moments delay, latency, latencyH1, taskTime;
 } fognet_user_stats;
+
+/* Statistics of ONE fog node in one replication (or, reduced, in one job): what the
+ * reference records per ComputeBroker module (ComputeBrokerApp3.ned:45-46).  A task is
+ * COMPLETED when its done_tick >= 0 (a node-down task that never completes has -1 and adds
+ * nothing to busy_s, resp or last_tick; a status-4 task with start_tick >= 0 still emits
+ * its queueTime).  Empty record: counts and sums 0, min_raw = INT64_MAX, max_raw =
+ * last_tick = INT64_MIN.  The exact merge of a replication's N records is its
+ * fognet_rep_stats: n_tasks, n_queued, n_started, busy_s sum; last_tick is the maximum;
+ * queue.{count, overflow} are n_qtime / n_qtime_overflow; the queue and resp limbs and
+ * extrema are the record's queue_* / resp_* (resp_sq_{lo,hi}: bits 0-127 of resp.sq). */
+typedef struct fognet_node_stats {
+    int64_t n_tasks;     /* decided publishes whose chosen node is this one                   */
+    int64_t n_queued;    /* ... with status 4                                                  */
+    int64_t n_started;   /* ... with status 5                                                  */
+    int64_t n_lost;      /* ... with status 9 (node-down)                                      */
+    int64_t busy_s;      /* service seconds req / MIPS_k (int division) of its COMPLETED tasks */
+    int64_t last_tick;   /* latest completion tick on this node; INT64_MIN if none             */
+    fognet_moments queue;/* this module's queueTime emissions, raw values ("Reference signal
+                            values"): status-4 tasks that started, enqueued at arrive + dl_k,
+                            started at start_tick; overflow = emissions the reference throws on */
+    fognet_moments resp; /* done_tick - arrive_tick (ticks) of its completed tasks; overflow 0  */
+} fognet_node_stats;     /* 192 B, 8-B aligned */
 
 /* ---- v2 model replay: BrokerBaseApp2 + ComputeBrokerApp2,
  * the modules simulations/example/wirelessNet.ini:56,62 select.  The broker
@@ -473,6 +498,32 @@ int fognet_run_batch(fognet_ctx *ctx, const fognet_batch_in *in, fognet_batch_ou
 int fognet_user_stats_dev(fognet_ctx *ctx, const fognet_batch_in *in, const fognet_batch_out *out,
                           const int64_t *user_ul_tick, const int64_t *user_dl_tick, int32_t user_per_task,
                           fognet_user_stats *user_stats, void *hip_stream);
+
+/* Per-node statistics from a finished replay (fognet_run_batch_dev, or fognet_replay_dev
+ * followed by fognet_rep_stats_dev, on the same stream): device pointers in `in`
+ * (arrive_tick, req_mips, mips, dl_tick) and `out` (node, status, start_tick, done_tick,
+ * stats[r].{n_tasks,status}).  Writes node_stats [R][N] (device): row r holds the records
+ * of replication r's nodes over its first stats[r].n_tasks publishes; a failed
+ * replication (status other than FOGNET_OK / FOGNET_REF_ABORTED) gets N empty records
+ * and nothing of its per-task rows is read.  FOGNET_POLICY_REF_V3 and
+ * FOGNET_POLICY_EXT_LAT, with or without down_tick.  Refused: FOGNET_POLICY_EXT_HIER
+ * (FOGNET_ERR_UNSUPPORTED: an escalated task reaches its node hier_up_tick later, and the
+ * per-task outputs do not say which tasks were escalated), a statistics-only `out`
+ * (FOGNET_ERR_ARG) and a NULL node_stats with R * N > 0 (FOGNET_ERR_ARG).
+ * FOGNET_NODE_STATS=hbm (environment, testing): the accumulators are the caller's
+ * records for every N, as they are above 256 nodes; the results are identical. */
+int fognet_node_stats_dev(fognet_ctx *ctx, const fognet_batch_in *in, const fognet_batch_out *out,
+                          fognet_node_stats *node_stats, void *hip_stream);
+/* Job reduction of the per-node records (device pointers): out[j] = the exact merge of
+ * node_stats[r][j] over the replications with stats[r].status == FOGNET_OK
+ * (fognet_reduce_stats_dev's rule: REF_ABORTED and failed ones contribute nothing).
+ * Any R; R = 0 gives N empty records.  Needs no workspace. */
+int fognet_reduce_node_stats_dev(fognet_ctx *ctx, const fognet_node_stats *node_stats,
+                                 const fognet_rep_stats *stats, int32_t R, int32_t N,
+                                 fognet_node_stats *out, void *hip_stream);
+/* Host-side identity and exact merge (ranks combine their [N] records after an all-gather). */
+void fognet_node_stats_init(fognet_node_stats *s);
+void fognet_node_stats_merge(fognet_node_stats *acc, const fognet_node_stats *other);
 
 /* Exact reduction of R per-replication stats (device pointers) into one job
  * record (device pointer).  Replications with status != OK count in n_failed

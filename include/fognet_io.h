@@ -87,6 +87,18 @@ int fognet_trace_read(const char *path, fognet_batch_in *out, int32_t *node_id);
 int fognet_write_sca(const char *path, const char *run_id, const char *network, const fognet_job_stats *job,
                      const int64_t *hist /* [FOGNET_HIST_METRICS][FOGNET_HIST_BINS], nullable */);
 
+/* OMNeT++ .sca blocks of per-node records (host; fognet_node_stats_dev /
+ * fognet_reduce_node_stats_dev, fognet_hip.h): per module
+ * <network>.fogNode[<node_id or index>].udpApp[0] (fognet_write_vec's naming) the
+ * scalars tasks, tasks queued, tasks started, tasks lost and busy seconds, then
+ * `queueTime:stats` and `response:stats` with fognet_write_sca's fields and
+ * formatting (a node without a task writes them with count 0).  append != 0: the
+ * blocks are appended to the existing file fognet_write_sca wrote, without a
+ * second version/run header; otherwise the file is created with one.
+ * node_id: [N], nullable (index names). */
+int fognet_write_sca_nodes(const char *path, const char *run_id, const char *network, int32_t N,
+                           const fognet_node_stats *nodes, const int32_t *node_id, int append);
+
 /* OMNeT++ .vec of one replication's per-task outputs (host arrays of length
  * T): vector `queueTime:vector` of every fog node module
  * <network>.fogNode[<node_id or index>].udpApp[0] (value ms, emitted at the
