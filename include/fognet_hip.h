@@ -188,9 +188,14 @@ typedef struct fognet_rep_stats {
     /* The reference's abort point (see "Reference signal values"): the RELEASERESOURCE
      * tick at which the first overflowing queueTime emission throws and the index of the
      * task it would have started; INT64_MAX / -1 when the reference run completes.
-     * Several overflowing emissions at that tick (different nodes): the lowest task index
-     * (the reference throws at the first in FES insertion order, which this does not
-     * resolve; the tick and so the reference-defined prefix are the same). */
+     * Several overflowing emissions at that tick (different nodes): abort_task is the LOWEST
+     * task index among them.  The reference, run under a stand-in kernel, throws at the one
+     * whose RELEASERESOURCE timer was inserted first (FES order: the node whose running
+     * service started earlier), which can be a higher index: in the recording
+     * overflow_same_tick_high_first (tests/golden/ref_v3_edges.json) it throws at task 5
+     * while task 3 overflows at the same tick, and this field is 3.  The tick, and so the
+     * reference-defined prefix, are the same either way; the oracle's stop-at-abort mode
+     * names the reference's task. */
     int64_t abort_tick;
     int64_t abort_task;
 } fognet_rep_stats;

@@ -7,12 +7,14 @@
  * HIP engine in fognetsimpp_amd/ and the `cpu_baseline` leg of bench.py.
  * Nothing in the product path may link, load or call this code.
  *
- * Parity status: the reference cannot be built or run in this image (it needs
- * OMNeT++ 4.6 + INET 3.3; stand-in headers are not allowed) and it ships no
- * tests and no result files for the v3 modules.  This restatement is therefore
- * pinned only by hand-traced known-answer vectors derived from the reference
- * source (tests/golden/kat_*.json) — formally "parity unpinned" against an
- * executable reference.  See DESIGN.md §2.
+ * Parity status: the reference's own handlers, compiled in place against a
+ * stand-in for OMNeT++ 4.6 + INET 3.3 and run event by event (oracle/ref_shim/,
+ * `make ref`), agree with this restatement on every value they define
+ * (tests/test_reference_pin.py: committed recordings tests/golden/ref_v3_*.json,
+ * and live runs where the harness binary exists).  That pins the handler logic;
+ * SimTime arithmetic, fixed-latency links and same-tick delivery order are the
+ * project's written model in both.  Hand-traced known-answer vectors
+ * (tests/golden/kat_*.json) pin it besides.  See DESIGN.md §2.
  */
 #ifndef FOGNET_ORACLE_H
 #define FOGNET_ORACLE_H
@@ -126,7 +128,9 @@ typedef struct {
     int64_t abort_tick;           /* the reference's abort point: tick of the first
                                      overflowing emission (INT64_MAX: none) ...          */
     int64_t abort_task;           /* ... and the task it would have started (-1: none);
-                                     at one tick the lowest index (fognet_hip.h)         */
+                                     run to the end: the lowest index overflowing at that
+                                     tick (fognet_hip.h); stop_at_ref_abort: the first in
+                                     FES order, the one the reference throws at          */
 } orc_rep_stats;
 
 /* OMNeT++ 4.6 SimTime at the default scale 1e-12 (include/simtime.h, not in the

@@ -100,6 +100,30 @@ def check_qtime_record(st, exp):
     assert int(st["abort_tick"]) == ab and int(st["abort_task"]) == exp["abort_task"]
 
 
+def ref_v3_replay_cases():
+    """tests/golden/ref_v3_*.json but the decide file (make_ref_v3_fixtures.py): traces and
+    what the reference's own handlers did with them.  (name, trace, user_ul, user_dl, ref):
+    the trace is one replication (1-D arrays), the user links are [1] or [T]."""
+    import glob
+    out = []
+    for path in sorted(glob.glob(os.path.join(GOLDEN, "ref_v3_*.json"))):
+        if path.endswith("ref_v3_decide.json"):
+            continue
+        for c in json.load(open(path))["cases"]:
+            tr = dict(arrive=np.array(c["arrive"], np.int64), req=np.array(c["req"], np.int32),
+                      mips=np.array(c["mips"], np.int32), dl=np.array(c["dl"], np.int64),
+                      ul=np.array(c["ul"], np.int64), init=np.array(c["init"], np.int64))
+            out.append((c["name"], tr, np.array(c["user_ul"], np.int64), np.array(c["user_dl"], np.int64), c["ref"]))
+    return out
+
+
+def ref_v3_decide_cases():
+    """tests/golden/ref_v3_decide.json: (name, busy, mips, req, node) as the reference decided."""
+    d = json.load(open(os.path.join(GOLDEN, "ref_v3_decide.json")))
+    return [(c["name"], np.array([_f(x) for x in c["busy"]], np.float64), np.array(c["mips"], np.int32),
+             int(c["req"]), int(c["node"])) for c in d["cases"]]
+
+
 def general0_v2_node():
     """tests/golden/general0_v2_node.json (make_general0_fixture.py): the fog node
     of the reference's recorded example run (ComputeBrokerApp2 timing)."""

@@ -1816,3 +1816,112 @@ def test_generated_wide_paths_equal_materialized(ctx, kind):
         assert (st["status"] == _abi.FOGNET_ERR_ARG).all()
     assert gen.rep_stats().tobytes() == st.tobytes()
     assert torch.equal(gen.hist, ref.hist) and torch.equal(gen.node_energy, ref.node_energy)
+
+
+# ------------------------------------------------------------------ the reference's own handlers, recorded
+# tests/golden/ref_v3_*.json (make_ref_v3_fixtures.py): BrokerBaseApp3 / ComputeBrokerApp3 compiled in
+# place and run under a stand-in kernel.  The device is compared with the recording itself, not with
+# the oracle; nothing here reads the reference tree.
+
+REF_REPLAYS = golden_io.ref_v3_replay_cases()
+
+
+def _ref_device_trace(ctx, tr):
+    dev = torch.device("cuda", ctx.device)
+    return fa.as_device_trace(dict(tr, arrive=tr["arrive"][None], req=tr["req"][None]), dev)
+
+
+@pytest.mark.parametrize("kernel", ["register", "wide", "inloop", "separate"])
+def test_reference_recordings_gpu(ctx, monkeypatch, kernel):
+    """node, status, start and done on the prefix the reference run defines (all T tasks
+    where it does not abort), and the record: the queueTime moments from Python integers over
+    the recorded emissions where the run completes, the abort tick where it does not.  At a
+    same-tick double overflow abort_task is the lowest overflowing index of that tick, which
+    need not be the emission the reference threw at (overflow_same_tick_high_first: 3, not 5)."""
+    import ref_harness as rh
+    if kernel == "wide":
+        monkeypatch.setenv("FOGNET_REPLAY_KERNEL", "wide")
+    if kernel == "inloop":
+        monkeypatch.setenv("FOGNET_REPLAY_STATS", "inloop")
+    big = np.iinfo(np.int64).max
+    compared = 0
+    for name, tr, uu, ud, rec in REF_REPLAYS:
+        d = _ref_device_trace(ctx, tr)
+        if kernel == "separate":
+            out = fa.run_batch(ctx, d, stage="replay", ring_capacity=4096)
+            fa.run_batch(ctx, d, out=out, stage="stats", ring_capacity=4096)
+        else:
+            out = fa.run_batch(ctx, d, ring_capacity=4096)
+        torch.cuda.synchronize()
+        st = out.rep_stats()[0]
+        assert st["status"] == 0, name
+        g = {k: getattr(out, a)[0].cpu().numpy().astype(np.int64)
+             for k, a in (("node", "node"), ("status", "status"), ("start", "start_tick"), ("done", "done_tick"))}
+        want = {k: np.array(rec[k], np.int64) for k in g}
+        defined = dict(node=want["node"] >= 0, status=want["status"] != 0, start=want["start"] >= 0,
+                       done=want["done"] >= 0)
+        for k in g:
+            np.testing.assert_array_equal(g[k][defined[k]], want[k][defined[k]], err_msg=f"{name} {k}")
+            compared += int(defined[k].sum())
+        ab = rec["abort"]
+        if ab is None:
+            assert all(m.all() for m in defined.values()), name
+            raws = [e[0] for e in rec["qtime"]]
+            assert rh.queue_moments_of(st) == dict(count=len(raws), min=min(raws) if raws else big,
+                                                   max=max(raws) if raws else -big - 1, sum=sum(raws),
+                                                   sq=sum(r * r for r in raws)), name
+            assert int(st["n_qtime_overflow"]) == 0 and int(st["abort_tick"]) == big and int(st["abort_task"]) == -1
+            assert int(st["n_queued"]) == rec["status"].count(4) and int(st["n_started"]) == rec["status"].count(5)
+        else:
+            assert int(st["abort_tick"]) == ab["tick"] and int(st["n_qtime_overflow"]) >= 1, name
+            # every publish up to the abort tick is decided in the reference run
+            assert defined["node"][tr["arrive"] <= ab["tick"]].all(), name
+            # the field: the lowest index among the emissions that overflow at that tick
+            at = [t for t in range(len(g["start"])) if g["status"][t] == 4 and g["start"][t] == ab["tick"]
+                  and ol.qtime_raw(ab["tick"], int(tr["arrive"][t]) + int(tr["dl"][g["node"][t]])) is None]
+            assert ab["task"] in at and int(st["abort_task"]) == min(at), name
+    assert compared >= sum(4 * len(c[1]["arrive"]) for c in REF_REPLAYS if c[4]["abort"] is None)
+
+
+def test_reference_recordings_user_stats_gpu(ctx):
+    """fognet_user_stats_dev against the acks the reference's broker relayed to the user and its
+    delay emissions, on the recordings that complete (past an abort the device's records hold
+    the extension's acks too)."""
+    import ref_harness as rh
+    n = 0
+    for name, tr, uu, ud, rec in REF_REPLAYS:
+        if rec["abort"] is not None:
+            continue
+        d = _ref_device_trace(ctx, tr)
+        out = fa.run_batch(ctx, d, ring_capacity=4096)
+        T = len(tr["arrive"])
+        shape = (1, T) if uu.size == T and T > 1 else (1,)
+        g = fa.user_stats(ctx, d, out, uu.reshape(shape), ud.reshape(shape))
+        want = rh.expected_user(tr, uu, ud, rec, ol.ms_raw)
+        for sig in ol.USER_SIGNALS:
+            assert rh.user_moments_of(g[0][sig]) == want[sig], (name, sig)
+        assert want["delay"]["count"] == T and want["taskTime"]["count"] == T
+        n += 1
+    assert n >= 11
+
+
+def test_reference_decisions_gpu(ctx):
+    """The reference's own decisions on arbitrary doubles (NaN, infinities, -0.0, denormals,
+    ties that appear only after the addition rounds) through fognet_decide, fognet_decide_window
+    and fognet_decide_batch_dev."""
+    cases = golden_io.ref_v3_decide_cases()
+    broker = fa.BrokerBaseApp3(ctx)
+    dev = torch.device("cuda", ctx.device)
+    by_n = {}
+    for name, busy, mips, req, node in cases:
+        assert broker.sendPubAck(busy, mips, req) == node, name
+        got = broker.sendPubAck_window(busy, mips, np.array([req, req], np.int32))
+        assert got.tolist() == [node, node], name
+        by_n.setdefault(len(busy), []).append((busy, mips, req, node))
+    for n, group in by_n.items():
+        busy = torch.from_numpy(np.stack([c[0] for c in group])).to(dev)
+        mips = torch.from_numpy(np.stack([c[1] for c in group])).to(dev)
+        req = torch.tensor([c[2] for c in group], dtype=torch.int32, device=dev)
+        node, status = broker.sendPubAck_batch(busy, mips, req)
+        assert (status.cpu().numpy() == 0).all(), n
+        assert node.cpu().numpy().tolist() == [c[3] for c in group], n
