@@ -309,6 +309,7 @@ int run_register(fognet_ctx* c, fognet::ReplayArgs& a, bool stats_only, hipStrea
   a.wide_list = w.list;
   a.ring = reinterpret_cast<fognet::RingWord*>(w.body);
   if (scratch_out) {
+    a.scratch_out = 1;
     a.out_node = w.out_node;
     a.out_status = w.out_status;
     a.out_start = w.out_start;

@@ -258,6 +258,9 @@ struct ReplayArgs {
   // task; the register kernel writes to an internal [R][T] scratch instead
   // (its fused statistics epilogue reads the outputs back).
   int32_t no_task_out;
+  // 1: out_node/out_status/out_start/out_done are that internal scratch, which
+  // nobody reads after the launch (the fused epilogue skips its write-back)
+  int32_t scratch_out;
   // FOGNET_POLICY_EXT_HIER (wide kernel): [R][T] regional broker per publish, escalation
   // threshold (advertised busy seconds) and the escalated task's extra latency
   const int32_t* region;

@@ -309,7 +309,8 @@ __device__ __forceinline__ uint32_t board_slot() {
 // Post progress `my` (wave-uniform) and set the priority from the SIMD's slots.
 __device__ __forceinline__ void board_update(uint32_t* board, uint32_t slot, uint32_t my, int lane) {
   if (lane == 0) __hip_atomic_store(board + slot, my, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const uint32_t l = (uint32_t)lane & 15u;
+  uint32_t l = (uint32_t)lane & 15u;
+  asm volatile("" : "+v"(l));  // (rebuilt at each update: hoisted, the lane's 64-bit address spills)
   const uint32_t v = __hip_atomic_load(board + (slot & ~15u) + l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const uint64_t behind = ballot(lane < 16 && l != (slot & 15u) && v < my);  // empty / finished slots hold ~0
   const uint32_t n = (uint32_t)__popcll(behind);
@@ -614,6 +615,9 @@ __device__ __forceinline__ void stats_finish(const ReplayArgs& A, int r, int64_t
 // vmcnt(0)).  The loop's tail-state LDS is dead now and holds the pass's
 // scratch: e_busy aliases s_tld, e_e s_ul, e_hist the chunk stage (>= 128
 // words), ab_t [64] i64 + ab_k [64] i32 a dead table of >= 768 B.
+// The chunk flush left the packed word of every pushed task in out_node
+// (replay_common.h, stats_accumulate_packed): the pass reads arrive, out_done
+// and the word, and stores the clean node back.
 template <int NPL>
 __device__ __forceinline__ void fused_stats_epilogue(const ReplayArgs& A, int r, int64_t n_done, uint32_t err,
                                                      int64_t* s_tld, const uint32_t* s_tlC, int64_t* s_ul,
@@ -626,16 +630,9 @@ __device__ __forceinline__ void fused_stats_epilogue(const ReplayArgs& A, int r,
   // completion (the tail's, FIFO) in the tail state: busy seconds, per-node
   // service for the energy model and `last` then need no per-task work.
   const bool from_tails = err == FOGNET_OK && (uint64_t)n_done * (uint64_t)A.max_s < (1ull << 32);
+  const bool write_back = !A.scratch_out;
   Acc acc = acc_identity();
-  if (from_tails) {
-    for (int j = lane; j < NPL * kWave; j += kWave) {
-      const uint32_t B = s_tlC[j];  // 0 for unused nodes and lanes past N
-      const int64_t ld = s_tld[j];  // INT64_MIN for unused nodes
-      acc.busy += B;
-      acc.last = max(acc.last, ld);
-      if (A.p_busy) e_busy[j] = B;  // aliases s_tld[j]: read above by this lane
-    }
-  } else if (A.p_busy) {
+  if (!from_tails && A.p_busy) {
     for (int j = lane; j < NPL * kWave; j += kWave) e_busy[j] = 0ull;
   }
   if (A.hist)
@@ -644,12 +641,22 @@ __device__ __forceinline__ void fused_stats_epilogue(const ReplayArgs& A, int r,
   ab_t[lane] = INT64_MAX;
   ab_k[lane] = INT32_MAX;
   __syncthreads();
-  if (from_tails)
-    stats_accumulate<4, false>(A, tbase, (int)n_done, lane, kWave, acc, e_busy, e_hist,
-                               [&](int k) { return s_dl[k]; }, ab_t, ab_k);
-  else
-    stats_accumulate<4>(A, tbase, (int)n_done, lane, kWave, acc, e_busy, e_hist, [&](int k) { return s_dl[k]; },
-                        ab_t, ab_k);
+  if (from_tails) {
+    stats_accumulate_packed<4, false>(A, tbase, (int)n_done, lane, write_back, acc, e_busy, e_hist,
+                                      [&](int k) { return s_dl[k]; }, ab_t, ab_k);
+    // (after the pass, which touches neither the tails nor e_busy here: its
+    // loop then carries no busy and `last` accumulators)
+    for (int j = lane; j < NPL * kWave; j += kWave) {
+      const uint32_t B = s_tlC[j];  // 0 for unused nodes and lanes past N
+      const int64_t ld = s_tld[j];  // INT64_MIN for unused nodes
+      acc.busy += B;
+      acc.last = max(acc.last, ld);
+      if (A.p_busy) e_busy[j] = B;  // aliases s_tld[j]: read above by this lane
+    }
+  } else {
+    stats_accumulate_packed<4, true>(A, tbase, (int)n_done, lane, write_back, acc, e_busy, e_hist,
+                                     [&](int k) { return s_dl[k]; }, ab_t, ab_k);
+  }
   const AbortPt ab = wave_min_abort(AbortPt{ab_t[lane], ab_k[lane]});  // (each lane's own slot)
   acc = wave_merge(acc);
   __syncthreads();
@@ -664,10 +671,27 @@ __device__ __forceinline__ void fused_stats_epilogue(const ReplayArgs& A, int r,
 // per-task outputs are still stored unless A.no_task_out.
 // GEN (implies INL): generated mode (ReplayArgs::gen_on): the trace chunks
 // and node parameters are computed here, and nothing is stored per task.
+// EPI (replay_kernel only): the fused statistics epilogue follows the loop
+// (ReplayArgs::fuse_stats with a stats record), so the chunk flush stores the
+// packed word it reads (pack_task) into out_node and the epilogue stores the
+// clean node back.  Every path that skips the epilogue leaves clean outputs:
+// a replay-only launch (EPI = false) flushes the plain node; a precondition
+// error runs the epilogue over the n_done pushed tasks, exactly the ones
+// flushed; a hand-over (kNeedsWide) leaves packed words behind, and the wide
+// kernel, which replays a listed replication from its first publish under the
+// same preconditions, stores all four outputs of every task it pushes
+// (replay_wide.hip, the lane-0 store of a single publish and the chunk's
+// output stores), so it overwrites every word written here.
 // r: the replication; slot: its pending-task rings in the workspace.
-template <int NPL, int POL, bool GEN, bool INL>
+template <int NPL, int POL, bool GEN, bool INL, bool EPI = false>
 __device__ __forceinline__ void replay_body(const ReplayArgs& A, const int r, const int slot) {
   static_assert(INL || !GEN, "generated mode accumulates in the loop");
+  static_assert(!EPI || (!GEN && !INL), "the fused epilogue belongs to replay_kernel");
+#if !defined(FOGNET_REPLAY_PROFILE) || FOGNET_REPLAY_PROFILE == 0 || FOGNET_REPLAY_PROFILE == 3
+  constexpr bool kPack = EPI;
+#else
+  constexpr bool kPack = false;  // (profile builds 1 and 2 have no epilogue)
+#endif
   constexpr bool kExt = POL == FOGNET_POLICY_EXT_LAT;
   constexpr int kSet = INL ? 4 : 0;  // prefetch register set
   const int lane = threadIdx.x;
@@ -1161,9 +1185,11 @@ __device__ __forceinline__ void replay_body(const ReplayArgs& A, const int r, co
           const int64_t dn = s_od[lane];
           // nontemporal: the outputs are re-read only by the epilogue, long
           // after they left L2; the ring's head lines keep the cache
-          __builtin_nontemporal_store((int32_t)s_on[lane], (A.out_node + o) + l);
+          const uint32_t sS = s_oS[lane];
+          const uint32_t nd = kPack ? pack_task(s_on[lane], sS, so) : (uint32_t)s_on[lane];
+          __builtin_nontemporal_store((int32_t)nd, (A.out_node + o) + l);
           __builtin_nontemporal_store((uint8_t)so, (A.out_status + o) + l);
-          __builtin_nontemporal_store(dn - ticks_of(s_oS[lane]), (A.out_start + o) + l);
+          __builtin_nontemporal_store(dn - ticks_of(sS), (A.out_start + o) + l);
           __builtin_nontemporal_store(dn, (A.out_done + o) + l);
           s_os[lane] = 0u;
         }
@@ -1276,9 +1302,10 @@ __device__ __forceinline__ void replay_body(const ReplayArgs& A, const int r, co
       if (lane == 0) write_rep_stats(S, gacc, AbortPt{s_ab_tick[0], s_ab_task[0]}, A.ref_abort);
       stats_finish(A, r, n_done > 0 ? gacc.last : 0, S, e_busy, e_e, s_hs, lane, kWave);
     }
-  } else if (A.fuse_stats && A.out_stats && err != kNeedsWide) {
-    fused_stats_epilogue<NPL>(A, r, n_done, err, s_tld, s_tlC, s_ul, s_dl, s_ch,
-                              reinterpret_cast<int64_t*>(kAbInDvm ? (void*)s_dvm : (void*)s_abx), lane);
+  } else if constexpr (kPack) {
+    if (err != kNeedsWide)
+      fused_stats_epilogue<NPL>(A, r, n_done, err, s_tld, s_tlC, s_ul, s_dl, s_ch,
+                                reinterpret_cast<int64_t*>(kAbInDvm ? (void*)s_dvm : (void*)s_abx), lane);
   }
 #endif
 #if FOGNET_REPLAY_PROFILE == 3
@@ -1299,9 +1326,11 @@ __device__ __forceinline__ void replay_body(const ReplayArgs& A, const int r, co
 // replications resident per CU, so the 4096-replication sweep runs in a single
 // wave of workgroups on 256 CUs.  (11 KiB of LDS admits only 14 per CU, and
 // the last 512 replications then run as a second, mostly idle round.)
-template <int NPL, int POL>
+// EPI: with the fused statistics epilogue (a template flag: the flush of a
+// replay-only launch stores the plain node without a run-time test).
+template <int NPL, int POL, bool EPI>
 __global__ __launch_bounds__(64, 4) __attribute__((amdgpu_num_vgpr(kNhBase / 2))) void replay_kernel(ReplayArgs A) {
-  replay_body<NPL, POL, false, false>(A, blockIdx.x, blockIdx.x);
+  replay_body<NPL, POL, false, false, EPI>(A, blockIdx.x, blockIdx.x);
 }
 
 // Statistics in the loop (ReplayArgs::inloop): 3 waves per SIMD like the
@@ -1370,6 +1399,17 @@ __global__ __launch_bounds__(kStatThreads) void rep_stats_kernel(ReplayArgs A) {
 
 }  // namespace
 
+template <int POL, bool EPI>
+void launch_replay_kernel(const ReplayArgs& a, int npl, hipStream_t s) {
+  if (npl <= 1) {
+    hipLaunchKernelGGL((replay_kernel<1, POL, EPI>), dim3(a.R), dim3(kWave), 0, s, a);
+  } else if (npl == 2) {
+    hipLaunchKernelGGL((replay_kernel<2, POL, EPI>), dim3(a.R), dim3(kWave), 0, s, a);
+  } else {
+    hipLaunchKernelGGL((replay_kernel<4, POL, EPI>), dim3(a.R), dim3(kWave), 0, s, a);
+  }
+}
+
 template <int POL>
 void launch_replay_pol(const ReplayArgs& a, hipStream_t s) {
   const int npl = (a.N + kWave - 1) / kWave;
@@ -1392,13 +1432,10 @@ void launch_replay_pol(const ReplayArgs& a, hipStream_t s) {
       hipLaunchKernelGGL((replay_inl_kernel<4, POL>), dim3(a.R), dim3(kWave), 0, s, a);
     return;
   }
-  if (npl <= 1) {
-    hipLaunchKernelGGL((replay_kernel<1, POL>), dim3(a.R), dim3(kWave), 0, s, a);
-  } else if (npl == 2) {
-    hipLaunchKernelGGL((replay_kernel<2, POL>), dim3(a.R), dim3(kWave), 0, s, a);
-  } else {
-    hipLaunchKernelGGL((replay_kernel<4, POL>), dim3(a.R), dim3(kWave), 0, s, a);
-  }
+  if (a.fuse_stats && a.out_stats)
+    launch_replay_kernel<POL, true>(a, npl, s);
+  else
+    launch_replay_kernel<POL, false>(a, npl, s);
 }
 
 hipError_t launch_replay(const ReplayArgs& a, hipStream_t s) {

@@ -409,8 +409,9 @@ __device__ __forceinline__ void write_rep_stats(fognet_rep_stats* S, const Acc& 
 }
 
 // ---------------------------------------------------------------- statistics pass
-// The statistics pass over the replay outputs (replay.hip's fused epilogue and
-// rep_stats_kernel, replay_region.hip's finish kernel).
+// The statistics pass over the replay outputs (replay.hip's rep_stats_kernel,
+// replay_region.hip's finish kernel; replay_kernel's fused epilogue runs the
+// packed form below, stats_accumulate_packed).
 
 // Accumulate tasks i = i0, i0 + stride, ... < n of one replication into `a`
 // (plus the per-node service seconds s_busy and the histogram s_hist in LDS
@@ -467,6 +468,110 @@ __device__ __forceinline__ void stats_accumulate(const ReplayArgs& A, size_t tba
         }
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------- packed statistics pass
+// replay_kernel's fused epilogue (replay.hip) reads one packed word per task
+// instead of the node, status and start arrays: the chunk flush stores
+// node | S << 8 | status << 16 into out_node (node < 256; S < 256 service
+// seconds while the replication stays in the register kernel; status 4 or 5),
+// so start = done - S * 1e12 needs no load and the service no division.  The
+// pass reads three streams (arrive, out_done, the word: 20 B/task) and stores
+// the clean node back, so out_node is what the other kernels write by the time
+// the kernel returns.
+__device__ __forceinline__ uint32_t pack_task(uint32_t node, uint32_t S, uint32_t status) {
+  return node | (S << 8) | (status << 16);
+}
+
+template <int UNROLL>
+struct PackedRows {  // UNROLL x 5 dwords
+  int64_t t[UNROLL], dn[UNROLL];
+  uint32_t w[UNROLL];
+};
+
+// The block of UNROLL x 64 rows that starts at task ib of a replication with
+// n > 0 pushed tasks: row ib + u * 64 + lane (u < UNROLL).  The loads are
+// unconditional, so the compiler counts them in its waits: a row past the end
+// reloads task n - 1, and a block wholly past the end (the pipeline's last
+// prefetch) reloads block 0; neither is used.  The block's base is wave-uniform
+// and the lane's offset small, so no 64-bit address lives in a VGPR.
+template <int UNROLL>
+__device__ __forceinline__ void packed_load(PackedRows<UNROLL>& s, const int64_t* arrive, const int64_t* done,
+                                            const int32_t* word, uint32_t ib, uint32_t n, uint32_t lane) {
+  const uint32_t b = ib < n ? ib : 0u;
+  const uint32_t lim = n - 1u - b;
+#pragma unroll
+  for (int u = 0; u < UNROLL; ++u) {
+    const uint32_t o = min((uint32_t)(u * kWave) + lane, lim);
+    s.t[u] = (arrive + b)[o];
+    s.dn[u] = (done + b)[o];
+    s.w[u] = (uint32_t)(word + b)[o];
+  }
+}
+
+// One wavefront over the n pushed tasks of its replication (lane l: tasks l,
+// l + 64, ...).  The loop is software-pipelined over two register sets: the
+// loads of the next UNROLL x 64 rows are issued before the current rows are
+// used, so the only waits in the loop are counted ones for the older set.
+// write_back (wave-uniform): store the clean node; off for the internal
+// scratch outputs of a statistics-only replay, which nobody reads afterwards.
+// kPerTask, s_busy, s_hist, dl_of, ab_tick/ab_task (one slot per lane): as
+// stats_accumulate.
+template <int UNROLL, bool kPerTask, class DlOf>
+__device__ __forceinline__ void stats_accumulate_packed(const ReplayArgs& A, size_t tbase, int n_tasks, int lane_id,
+                                                        bool write_back, Acc& a, unsigned long long* s_busy,
+                                                        uint32_t* s_hist, DlOf dl_of, int64_t* ab_tick,
+                                                        int32_t* ab_task) {
+  if (n_tasks <= 0) return;
+  const uint32_t n = (uint32_t)n_tasks, lane = (uint32_t)lane_id & (uint32_t)(kWave - 1);
+  const bool energy = kPerTask && A.p_busy != nullptr;
+  const bool hist = A.hist != nullptr;
+  const int64_t* const arrive = A.arrive + tbase;
+  const int64_t* const done = A.out_done + tbase;
+  int32_t* const word = A.out_node + tbase;
+  auto rows = [&](const PackedRows<UNROLL>& s, uint32_t ib) {  // ib < n
+    const uint32_t lim = n - 1u - ib;
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const uint32_t o = (uint32_t)(u * kWave) + lane;
+      if (o <= lim) {
+        const uint32_t k = s.w[u] & 0xFFu, S = (s.w[u] >> 8) & 0xFFu, status = s.w[u] >> 16;
+        const int64_t start = s.dn[u] - ticks_of(S);
+        if (write_back) __builtin_nontemporal_store((int32_t)k, (word + ib) + o);
+        const int64_t resp = s.dn[u] - s.t[u];
+        if constexpr (kPerTask) {
+          a.busy += S;
+          if (energy) atomicAdd(&s_busy[k], (unsigned long long)S);
+          a.last = max(a.last, s.dn[u]);
+        }
+        add_moment(a.rs_lo, a.rs_hi, a.rq_lo, a.rq_hi, (uint64_t)resp);
+        a.rmin = min(a.rmin, resp);
+        a.rmax = max(a.rmax, resp);
+        if (hist) atomicAdd(&s_hist[FOGNET_HIST_BINS + hist_bin(resp)], 1u);
+        if (status == 4u) {  // queueTime emission (ComputeBrokerApp3.cc:238), enqueued at its arrival
+          a.n4 += 1u;
+          if (!acc_qtime(a.qs_lo, a.qs_hi, a.qq_lo, a.qq_hi, a.qq_top, a.qmin, a.qmax, a.nqt, a.nqo, start,
+                         s.t[u] + dl_of((int)k), hist ? s_hist : nullptr))
+            abort_min(ab_tick[lane], ab_task[lane], start, (int32_t)(ib + o));
+        } else {
+          a.n5 += 1u;
+        }
+      }
+    }
+  };
+  constexpr uint32_t kStep = UNROLL * kWave;  // (n < 2^31: ib + kStep does not wrap)
+  PackedRows<UNROLL> r0, r1;
+  packed_load(r0, arrive, done, word, 0u, n, lane);
+  for (uint32_t ib = 0u;;) {  // (wave-uniform control flow)
+    packed_load(r1, arrive, done, word, ib + kStep, n, lane);
+    rows(r0, ib);
+    ib += kStep;
+    if (ib >= n) break;
+    packed_load(r0, arrive, done, word, ib + kStep, n, lane);
+    rows(r1, ib);
+    ib += kStep;
+    if (ib >= n) break;
   }
 }
 

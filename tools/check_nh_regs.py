@@ -16,17 +16,18 @@ def regs_of(s):
 
 
 def audit(path):
-    return (audit_one(path, "_ZN6fognet12_GLOBAL__N_113replay_kernelILi", 112)
+    # replay_kernel<NPL, POL, EPI>: with and without the fused statistics epilogue
+    return (audit_one(path, "_ZN6fognet12_GLOBAL__N_113replay_kernelILi", 112, ("ELb0E", "ELb1E"))
             + audit_one(path, "_ZN6fognet12_GLOBAL__N_117replay_gen_kernelILi", 152)
             + audit_one(path, "_ZN6fognet12_GLOBAL__N_117replay_inl_kernelILi", 152))
 
 
-def audit_one(path, kernel_prefix, base):
+def audit_one(path, kernel_prefix, base, tails=("E",)):
     text = open(path).read().split("\n")
     bad_total = 0
     found = 0
-    for npl, pol in [(n, p) for n in (1, 2, 4) for p in (1, 16)]:  # policies REF_V3, EXT_LAT
-        name = f"{kernel_prefix}{npl}ELi{pol}EEEvNS_10ReplayArgsE"
+    for npl, pol, tail in [(n, p, t) for n in (1, 2, 4) for p in (1, 16) for t in tails]:  # policies REF_V3, EXT_LAT
+        name = f"{kernel_prefix}{npl}ELi{pol}{tail}EEvNS_10ReplayArgsE"
         starts = [i for i, ln in enumerate(text) if ln.startswith(f"{name}:")]
         if not starts:
             continue
@@ -60,11 +61,11 @@ def audit_one(path, kernel_prefix, base):
                 continue
             if not in_asm and regs_of(ln) & nh:
                 bad.append(ln)
-        print(f"{kernel_prefix[26:-3]} NPL={npl} policy={pol}: prefetch registers {sorted(nh)}; compiler references outside asm: {len(bad)}")
+        print(f"{kernel_prefix[26:-3]} NPL={npl} policy={pol} {tail[1:-1]}: prefetch registers {sorted(nh)}; compiler references outside asm: {len(bad)}")
         for b in bad[:20]:
             print("   ", b)
         bad_total += len(bad)
-    assert found == 6, f"expected 6 {kernel_prefix} instantiations in the ISA, found {found}"
+    assert found == 6 * len(tails), f"expected {6 * len(tails)} {kernel_prefix} instantiations in the ISA, found {found}"
     return bad_total
 
 
