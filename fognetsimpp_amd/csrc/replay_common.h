@@ -1,7 +1,8 @@
 // replay_common.h — device pieces shared by the two replay kernels:
 // replay.hip (N <= 256, node state in VGPRs) and replay_wide.hip (N <= 65,536,
-// node state in LDS + HBM).  Tick arithmetic, the FES same-tick rule and the
-// exact per-replication statistics accumulator.
+// node state in LDS + HBM).  Tick arithmetic, the FES same-tick rule, the
+// exact per-replication statistics accumulator, and the node chain model of
+// the wide and region kernels (adverts and pushes over WideNode / WideEntry).
 #pragma once
 
 #include "internal.h"
@@ -10,7 +11,7 @@ namespace fognet {
 
 constexpr int64_t kNever = INT64_MAX;
 // Simulated ticks are kept below 2^61 (26.7 days); service seconds enter the
-// tick arithmetic clamped (2^22 s in the wide kernel, 255 s in the register
+// tick arithmetic clamped (kChainSCap in the wide kernels, 255 s in the register
 // kernel), so no intermediate of the replay arithmetic can overflow int64.
 constexpr int64_t kMaxTick = (int64_t)1 << 61;
 
@@ -577,7 +578,8 @@ __device__ __forceinline__ void stats_accumulate_packed(const ReplayArgs& A, siz
 
 // ---------------------------------------------------------------- wide-record advert
 // (replay_wide.hip, replay_region.hip) Saturated advertised busy time in the
-// 32-bit view of the wide kernels.
+// 32-bit view of the wide kernels (also the busy value of the view's slots past
+// the node set, which never win: their index is larger).
 constexpr uint32_t kViewBusySat = 0xFFFFFFFFu;
 
 // The advert of node j's head completion reaches the broker (owner lane):
@@ -645,6 +647,106 @@ __device__ __forceinline__ bool apply_wide_advert(WideNode& h, const WideEntry* 
     nxt_j = nx.done == kNever ? kNever : nx.done + ul;  // never: crashed before it completes
   }
   return busy < ((uint64_t)1 << 24);  // FOGNET_POLICY_EXT_LAT's cost needs busy < 2^24
+}
+
+// ---------------------------------------------------------------- node chain model
+// (replay_wide.hip, replay_region.hip) A fog node's side of a push: FIFO single
+// server (ComputeBrokerApp3.cc:269-320) over its record (WideNode) and task chain
+// (WideEntry).  Views, range policy and outputs stay with each kernel.
+
+// Service seconds are any int / int (ComputeBrokerApp3.cc:276: up to 2^31 - 1).
+// The tick arithmetic clamps them at kChainSCap: a task served with a service time
+// (or a run prefix) of 2^22 s or more completes past kMaxTick (2^61 ticks = 26.7
+// days, 2^22 s = 48.5 days) and the wide kernel refuses that completion (the region
+// kernel hands the replication over), so the clamp never changes a result; the
+// cumulative service sums (advertised busy values) stay exact in 64 bits.
+constexpr uint32_t kChainSCap = 1u << 22;
+
+// Status of a task arriving at tick a (downlink dl, an escalated task's hop included)
+// behind a task done at prev_done with service prev_S (clamped by the caller): idle,
+// "task assigned" (ComputeBrokerApp3.cc:282-301); busy, "task queued" (:304-313); a
+// completion at the same tick by the FES insertion order (arrives_before).
+__device__ __forceinline__ uint32_t arrival_status(int64_t prev_done, uint32_t prev_S, int64_t a, int64_t dl) {
+  if (prev_done < a) return 5u;
+  if (prev_done > a) return 4u;
+  return dl < (int64_t)prev_S * kTicksPerSecond ? 5u : 4u;
+}
+
+// Node k's tail as every lane needs it for a run, from its owner lane kl's cached
+// record.  base_done: the completion the run queues behind (INT64_MIN: no task yet;
+// kNever: the node crashed with work left).  tl_S keeps the record's bit 31.
+struct ChainTail {
+  int32_t tl, npend;
+  int64_t tl_done, base_done;
+  uint64_t tl_C;
+  uint32_t tl_S;
+};
+
+__device__ __forceinline__ ChainTail chain_tail(const WideNode& ch, int kl) {
+  ChainTail t;
+  t.tl = (int32_t)readlane_u32((uint32_t)ch.tl, kl);
+  t.npend = (int32_t)readlane_u32((uint32_t)ch.npend, kl);
+  t.tl_done = readlane_i64(ch.tl_done, kl);
+  t.tl_C = (uint64_t)readlane_i64((int64_t)ch.tl_C, kl);
+  t.tl_S = readlane_u32(ch.tl_S, kl);
+  t.base_done = t.tl >= 0 ? t.tl_done : INT64_MIN;
+  return t;
+}
+
+// FIFO recurrence of a run, one lane per task (in_run; one: a single task needs no
+// wave scan): done_m = max(base, max_{i<=m} (a_i - P_{i-1})) + P_m with P the
+// inclusive prefix of the clamped service seconds Sd (run_prefix: < 64 * 2^22) and
+// `before` the ticks of P_{m-1} (run_dmax: the max term).  run_prev: the task each lane
+// queues behind, the lane before it (first: the run's first lane keeps the node's tail),
+// from the completion ticks dn that each kernel forms under its own range policy.
+__device__ __forceinline__ uint32_t run_prefix(bool in_run, bool one, uint32_t Sd) {
+  return one ? (in_run ? Sd : 0u) : wave_scan_add_u32(in_run ? Sd : 0u);
+}
+
+__device__ __forceinline__ int64_t run_dmax(bool in_run, bool one, int64_t a, int64_t before, int64_t base_done) {
+  int64_t X = in_run ? (int64_t)((uint64_t)a - (uint64_t)before) : INT64_MIN;
+  if (!one) X = wave_scan_max_i64(X);
+  return base_done > X ? base_done : X;
+}
+
+__device__ __forceinline__ void run_prev(bool one, bool first, int64_t dn, uint32_t Sd, int64_t& prev_done,
+                                         uint32_t& prev_S) {
+  if (one) return;  // (wave-uniform)
+  const int64_t dn_up = dpp_or_i64<kDppWaveShr1>(0, dn);
+  const uint32_t S_up = dpp_or_u32<kDppWaveShr1>(0u, Sd);
+  if (!first) {
+    prev_done = dn_up;
+    prev_S = S_up;
+  }
+}
+
+// Node record h after a run of Lr tasks i0 .. iz (consecutive entries, linked to each
+// other and to the old tail) was pushed behind its tail.  done_f, C_f, S_f: the run's
+// first task; a_z, done_z, C_z, S_z: its last (S_z with the record's bit 31).  Returns
+// whether the first task became the node's head: its advert is then the node's next one.
+__device__ __forceinline__ bool chain_append(WideNode& h, WideEntry* e, int i0, int iz, int Lr, int64_t done_f,
+                                             uint64_t C_f, uint32_t S_f, int64_t a_z, int64_t done_z, uint64_t C_z,
+                                             uint32_t S_z) {
+  const bool head = h.npend == 0;
+  if (head) {
+    h.hd = i0;
+    h.hd_done = done_f;
+    h.hd_C = C_f;
+    h.hd_S = S_f;
+  } else if (h.npend >= 2) {
+    e[h.tl].next = i0;
+  }
+  // hd_next after the two-way branch, not in a third arm (DESIGN.md §3.6 "The hd_next
+  // miscompile"): the run's second task on an idle node, its first on a node whose one
+  // pending task is the tail
+  if (h.npend == 1 || (h.npend == 0 && Lr > 1)) h.hd_next = h.npend == 1 ? i0 : i0 + 1;
+  h.tl = iz;
+  h.tl_a = a_z;
+  h.tl_done = done_z;
+  h.tl_C = C_z;
+  h.tl_S = S_z;
+  h.npend += Lr;
+  return head;
 }
 
 // ---------------------------------------------------------------- a11 energy over node records

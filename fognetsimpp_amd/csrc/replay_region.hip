@@ -44,8 +44,6 @@ namespace {
 
 constexpr int kRegionSlots = FOGNET_HIER_REGION_NODES / kWave;  // 16 view slots per lane
 static_assert(kRegionSlots == kWideGroupSlots, "a region is one wide-kernel group row");
-constexpr uint32_t kRegBusySat = 0xFFFFFFFFu;
-constexpr uint32_t kRegSCap = 1u << 22;  // the wide kernel's kWideSCap: past it the sequential kernel decides
 // Run-horizon offsets are capped (replay_wide.hip's node_w caps at 2^21 s): a smaller offset only
 // shortens runs.  16 bits here, so the view ticks and offsets take 10 KiB of LDS per wavefront and
 // 16 wavefronts fit per CU (12 KiB with 32-bit offsets: 13); C5's offsets are minutes at most.
@@ -284,7 +282,7 @@ __global__ __launch_bounds__(64, 4) void replay_region_kernel(ReplayArgs A, Regi
     const int l = s * kWave + lane;
     vnxt[s * kWave] = kNever;
     vwoff[s * kWave] = 0u;
-    vbusy[s * kWave] = l < nb ? 0u : kRegBusySat;  // (past the region: never the minimum)
+    vbusy[s * kWave] = l < nb ? 0u : kViewBusySat;  // (past the region: never the minimum)
     nzb |= l < nb ? 0u : 1u << s;
     if (l < nb) {
       const int j = base + l;
@@ -461,10 +459,10 @@ __global__ __launch_bounds__(64, 4) void replay_region_kernel(ReplayArgs A, Regi
           key = wave_min_u64(mk);
           view_changed = false;
         }
-        if ((key >> 32) > (uint64_t)A.hier_thr || (key >> 32) >= kRegBusySat) {
+        if ((key >> 32) > (uint64_t)A.hier_thr || (key >> 32) >= kViewBusySat) {
           err = kRegionSeq;
           // an escalation (publish s0 + c0 + jp), or a saturated view (the sequential kernel refuses it)
-          esc_hit = (key >> 32) >= kRegBusySat ? 0 : W.s_idx[tbase + s0 + c0 + jp];
+          esc_hit = (key >> 32) >= kViewBusySat ? 0 : W.s_idx[tbase + s0 + c0 + jp];
           break;
         }
       }
@@ -477,24 +475,19 @@ __global__ __launch_bounds__(64, 4) void replay_region_kernel(ReplayArgs A, Regi
       cache_node(k, kl);
       const UDiv div_k{readlane_u32(c_dv.m, kl), readlane_u32(c_dv.sh, kl)};
       const int64_t dl_k = readlane_i64(c_dl, kl), ul_k = readlane_i64(c_ul, kl);
-      const int32_t tl = (int32_t)readlane_u32((uint32_t)ch.tl, kl);
-      const int32_t npend0 = (int32_t)readlane_u32((uint32_t)ch.npend, kl);
-      const int64_t tl_done = readlane_i64(ch.tl_done, kl);
-      const uint64_t tl_C = (uint64_t)readlane_i64((int64_t)ch.tl_C, kl);
-      const uint32_t tl_S = readlane_u32(ch.tl_S, kl);
-      const int64_t base_done = tl >= 0 ? tl_done : INT64_MIN;
+      const ChainTail kt = chain_tail(ch, kl);
       if (!resume) {
         // k's own next advert changes its key; when k is idle the run's first task becomes its
         // head and that task's advert ends the run
         int64_t kb;
-        if (npend0 > 0) {
+        if (kt.npend > 0) {
           kb = readlane_i64(ch.hd_done, kl) + ul_k;
         } else {
           const uint32_t S0 = udiv(readlane_u32((uint32_t)cr, jp), div_k);
           const int64_t a0 = t + dl_k;  // (<= 2^62)
-          const int64_t st0 = a0 > base_done ? a0 : base_done;
+          const int64_t st0 = a0 > kt.base_done ? a0 : kt.base_done;
           kb = kNever;  // (past the tick range the run is refused below anyway)
-          if (S0 < kRegSCap && st0 <= kMaxTick) kb = st0 + ticks_of(S0) + ul_k;  // (< 2^61 + 2^62 + 2^61)
+          if (S0 < kChainSCap && st0 <= kMaxTick) kb = st0 + ticks_of(S0) + ul_k;  // (< 2^61 + 2^62 + 2^61)
         }
         if (jp + 1 < cnt && readlane_i64(ca, jp + 1) > kb) {
           // the next publish comes after k's advert: a run of one, whatever the other nodes'
@@ -534,18 +527,16 @@ __global__ __launch_bounds__(64, 4) void replay_region_kernel(ReplayArgs A, Regi
         S = udiv((uint32_t)cr, div_k);  // double tskTime = requiredMIPS / MIPS (:276)
         a = ca + dl_k;
       }
-      // FIFO recurrence over the run: done_m = max(base, max_{i<=m} (a_i - P_{i-1})) + P_m
-      const uint32_t Cs = one ? S : wave_scan_add_u32(in_run ? min(S, kRegSCap) : 0u);  // (< 64 * 2^22)
+      // FIFO recurrence over the run (replay_common.h run_prefix)
+      const uint32_t Cs = run_prefix(in_run, one, min(S, kChainSCap));
       // a service prefix of 2^22 s or more, or an arrival past 2^61 ticks, puts the run past the
       // tick range (the wide kernel's kPastRange): the sequential kernel decides the replication
-      if (ballot(in_run && (Cs >= kRegSCap || a > kMaxTick))) {
+      if (ballot(in_run && (Cs >= kChainSCap || a > kMaxTick))) {
         err = kRegionSeq;
         esc_hit = 0;
         break;
       }
-      int64_t X = in_run ? a - ticks_of(Cs - S) : INT64_MIN;
-      if (!one) X = wave_scan_max_i64(X);
-      const int64_t dmax = base_done > X ? base_done : X;
+      const int64_t dmax = run_dmax(in_run, one, a, ticks_of(Cs - S), kt.base_done);
       const int64_t start = dmax + ticks_of(Cs - S);
       const int64_t done = dmax + ticks_of(Cs);
       if (ballot(in_run && done > kMaxTick)) {
@@ -553,23 +544,14 @@ __global__ __launch_bounds__(64, 4) void replay_region_kernel(ReplayArgs A, Regi
         esc_hit = 0;
         break;
       }
-      int64_t prev_done = base_done;
-      uint32_t prev_S = tl_S;
-      if (!one) {
-        const int64_t dn_up = dpp_or_i64<kDppWaveShr1>(0, done);
-        const uint32_t S_up = dpp_or_u32<kDppWaveShr1>(0u, S);
-        if (lane != jp) {
-          prev_done = dn_up;
-          prev_S = S_up;
-        }
-      }
+      int64_t prev_done = kt.base_done;
+      uint32_t prev_S = kt.tl_S;
+      run_prev(one, lane == jp, done, S, prev_done, prev_S);
       uint32_t status = 0u;
       if (in_run) {
-        if (prev_done < a) status = 5u;       // idle: "task assigned" (:282-301)
-        else if (prev_done > a) status = 4u;  // busy: "task queued" (:304-313)
-        else status = dl_k < (int64_t)min(prev_S, kRegSCap) * kTicksPerSecond ? 5u : 4u;  // same-tick completion
+        status = arrival_status(prev_done, min(prev_S, kChainSCap), a, dl_k);
         const int i = s0 + c0 + lane;  // the task's sorted position: chained in order on node k
-        e[i] = WideEntry{a, done, tl_C + Cs, S, lane == jp ? tl : i - 1, lane + 1 < jq ? i + 1 : -1, 0};
+        e[i] = WideEntry{a, done, kt.tl_C + Cs, S, lane == jp ? kt.tl : i - 1, lane + 1 < jq ? i + 1 : -1, 0};
         q_on = true;
         q_k = k;
         q_status = status;
@@ -584,13 +566,9 @@ __global__ __launch_bounds__(64, 4) void replay_region_kernel(ReplayArgs A, Regi
       const uint32_t S_f = readlane_u32(S, jp);
       if (lane == kl) {
         WideNode h = ch;
-        const int i0 = s0 + c0 + jp, iz = s0 + c0 + lz;
         const int sk = ((int)k - base) / kWave;
-        if (h.npend == 0) {  // the run's first task is the node's head: its advert is the node's next one
-          h.hd = i0;
-          h.hd_done = done_f;
-          h.hd_C = tl_C + S_f;
-          h.hd_S = S_f;
+        if (chain_append(h, e, s0 + c0 + jp, s0 + c0 + lz, Lr, done_f, kt.tl_C + S_f, S_f, a_z, done_z, kt.tl_C + Cs_z,
+                         S_z)) {  // the run's first task is the node's head: its advert is the node's next one
           const int64_t x = done_f + ul_k;
           vnxt[sk * kWave] = x;
           act |= 1u << sk;
@@ -598,19 +576,7 @@ __global__ __launch_bounds__(64, 4) void replay_region_kernel(ReplayArgs A, Regi
             mn = x;
             ms = sk;
           }
-        } else if (h.npend >= 2) {
-          e[h.tl].next = i0;
         }
-        // hd_next after the two-way branch, not in a third arm (DESIGN.md §3.6 "The hd_next
-        // miscompile"): the run's second task on an idle node, its first on a node whose one
-        // pending task is the tail
-        if (h.npend == 1 || (h.npend == 0 && Lr > 1)) h.hd_next = h.npend == 1 ? i0 : i0 + 1;
-        h.tl = iz;
-        h.tl_a = a_z;
-        h.tl_done = done_z;
-        h.tl_C = tl_C + Cs_z;
-        h.tl_S = S_z;
-        h.npend += Lr;
         ch = h;
         max_pend = max(max_pend, (uint32_t)h.npend);
         vwoff[sk * kWave] = (uint16_t)w_offset(h, dl_k);  // k's horizon offset

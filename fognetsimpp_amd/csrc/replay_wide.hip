@@ -47,17 +47,8 @@ namespace fognet {
 
 namespace {
 
-// Service seconds are any int / int (ComputeBrokerApp3.cc:276: up to 2^31 - 1).
-// The tick arithmetic clamps them at kWideSCap: a task that is served with
-// a service time (or a run prefix) of 2^22 s or more completes past kMaxTick
-// (2^61 ticks = 26.7 days, 2^22 s = 48.5 days) and the replication is refused
-// by the completion-tick check, so the clamp never changes a result; the
-// cumulative service sums (advertised busy values) stay exact in 64 bits.
-constexpr uint32_t kWideSCap = 1u << 22;
-// Saturated advertised busy time in the 32-bit view (also the busy value of the
-// view's slots past N, which never win: their index is larger).
-constexpr uint32_t kBusySat = kViewBusySat;
-// A start or completion tick at or past base + 2^22 s (beyond kMaxTick).
+// A start or completion tick at or past base + 2^22 s (kChainSCap: beyond kMaxTick,
+// so the replication is refused by the completion-tick check).
 constexpr int64_t kPastRange = kMaxTick + 1;
 
 // Per-lane minima are kept in two levels: for each group of kWideGroupSlots
@@ -616,6 +607,23 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
     }
     return c;
   };
+  // node kk's pushed task became its head (owner lane): its advert, at tick x, is the node's next one
+  auto head_advert = [&](uint32_t kk, int64_t x) {
+    const int g = ((int)kk / kWave) / kWideGroupSlots;
+    V.nxt[kk / kWave] = x;
+    if (x != kNever) {
+      L.g_msk[g * kWave + lane] |= 1u << ((kk / kWave) % kWideGroupSlots);
+      gact.set(g, true);
+    }
+    if (x < L.g_nxt[g * kWave + lane]) {
+      L.g_nxt[g * kWave + lane] = x;
+      L.g_j[g * kWave + lane] = (int)kk;
+    }
+    if (x < mn) {
+      mn = x;
+      mj = (int)kk;
+    }
+  };
   // push escalated task i (publish tick t_i, MIPSRequired req_i) onto node kk; false: past kMaxTick
   auto push_one = [&](int i, int64_t t_i, uint32_t req_i, uint32_t kk) -> bool {
     cache_node(kk);
@@ -623,23 +631,17 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
     const UDiv div_k{readlane_u32((uint32_t)c_dv, kl), readlane_u32((uint32_t)(c_dv >> 32), kl)};
     const int64_t dl_k = readlane_i64(c_dl, kl) + A.hier_up;  // (the hop, then the downlink)
     const int64_t ul_k = readlane_i64(c_ul, kl), down_k = readlane_i64(c_down, kl);
-    const int32_t tl = (int32_t)readlane_u32((uint32_t)ch.tl, kl);
-    const int64_t tl_done = readlane_i64(ch.tl_done, kl);
-    const uint64_t tl_C = (uint64_t)readlane_i64((int64_t)ch.tl_C, kl);
-    const uint32_t tl_S = readlane_u32(ch.tl_S, kl) & 0x7FFFFFFFu;
-    const int64_t base_done = tl >= 0 ? tl_done : INT64_MIN;
+    const ChainTail kt = chain_tail(ch, kl);
     const uint32_t S = udiv(req_i, div_k);  // double tskTime = requiredMIPS / MIPS (ComputeBrokerApp3.cc:276)
     const int64_t a = t_i + dl_k;
-    const uint64_t C = tl_C + S;
+    const uint64_t C = kt.tl_C + S;
     int64_t start = kNever, done = kNever;
     uint32_t status = FOGNET_TASK_LOST;
-    if (base_done != kNever) {  // FIFO: start = max(arrival, previous completion)
-      const int64_t st = a > base_done ? a : base_done;
-      const int64_t dn = S < kWideSCap ? st + ticks_of(S) : kPastRange;
+    if (kt.base_done != kNever) {  // FIFO: start = max(arrival, previous completion)
+      const int64_t st = a > kt.base_done ? a : kt.base_done;
+      const int64_t dn = S < kChainSCap ? st + ticks_of(S) : kPastRange;
       if (a < down_k) {
-        if (base_done < a) status = 5u;
-        else if (base_done > a) status = 4u;
-        else status = dl_k < (int64_t)min(tl_S, kWideSCap) * kTicksPerSecond ? 5u : 4u;
+        status = arrival_status(kt.base_done, min(kt.tl_S & 0x7FFFFFFFu, kChainSCap), a, dl_k);
         start = st < down_k ? st : kNever;
         done = dn < down_k ? dn : kNever;
       }
@@ -647,39 +649,11 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
       status = 4u;
     }
     if (a > kMaxTick || (done != kNever && done > kMaxTick)) return false;
-    if (lane == 0) e[i] = WideEntry{a, done, C, S, tl, -1, 1};
+    if (lane == 0) e[i] = WideEntry{a, done, C, S, kt.tl, -1, 1};
     if (lane == kl) {
       WideNode h = ch;
-      if (h.npend == 0) {  // the node's head: its advert is the node's next one
-        h.hd = i;
-        h.hd_done = done;
-        h.hd_C = C;
-        h.hd_S = S;
-        const int64_t x = done == kNever ? kNever : done + ul_k;
-        const int g = ((int)kk / kWave) / kWideGroupSlots;
-        V.nxt[kk / kWave] = x;
-        if (x != kNever) {
-          L.g_msk[g * kWave + lane] |= 1u << ((kk / kWave) % kWideGroupSlots);
-          gact.set(g, true);
-        }
-        if (x < L.g_nxt[g * kWave + lane]) {
-          L.g_nxt[g * kWave + lane] = x;
-          L.g_j[g * kWave + lane] = (int)kk;
-        }
-        if (x < mn) {
-          mn = x;
-          mj = (int)kk;
-        }
-      } else if (h.npend >= 2) {
-        e[h.tl].next = i;
-      }
-      if (h.npend == 1) h.hd_next = i;  // the tail is the head (hoisted: DESIGN.md §3.6 "The hd_next miscompile")
-      h.tl = i;
-      h.tl_a = a;
-      h.tl_done = done;
-      h.tl_C = C;
-      h.tl_S = S | 0x80000000u;  // escalated
-      h.npend += 1;
+      if (chain_append(h, e, i, i, 1, done, C, S, a, done, C, S | 0x80000000u))  // (bit 31: escalated)
+        head_advert(kk, done == kNever ? kNever : done + ul_k);
       ch = h;
     }
     if (lane == 0 && !A.no_task_out) {
@@ -1005,7 +979,7 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
           glob_key = wave_min_u64(mk);
           glob_valid = true;
         }
-        if (((escalated ? glob_key : kb) >> 32) >= kBusySat) {  // the minimum is past 32 bits
+        if (((escalated ? glob_key : kb) >> 32) >= kViewBusySat) {  // the minimum is past 32 bits
           err = FOGNET_ERR_CAPACITY;
           break;
         }
@@ -1016,7 +990,7 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
         k_key = wave_min_u64(mk);
         k = (uint32_t)k_key;
         view_changed = false;
-        if ((k_key >> 32) >= kBusySat) {  // the minimum is past 32 bits: exact order unknown
+        if ((k_key >> 32) >= kViewBusySat) {  // the minimum is past 32 bits: exact order unknown
           err = FOGNET_ERR_CAPACITY;
           break;
         }
@@ -1072,12 +1046,8 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
       // (an escalated task takes the regional -> parent hop before the downlink)
       const int64_t dl_k = readlane_i64(c_dl, kl) + (escalated ? A.hier_up : 0);
       const int64_t ul_k = readlane_i64(c_ul, kl), down_k = readlane_i64(c_down, kl);
-      const int32_t tl = (int32_t)readlane_u32((uint32_t)ch.tl, kl);
-      const int32_t npend0 = (int32_t)readlane_u32((uint32_t)ch.npend, kl);
-      const int64_t tl_done = readlane_i64(ch.tl_done, kl);
-      const uint64_t tl_C = (uint64_t)readlane_i64((int64_t)ch.tl_C, kl);
-      const uint32_t tl_S = readlane_u32(ch.tl_S, kl) & 0x7FFFFFFFu;  // (bit 31: the tail was escalated)
-      const int64_t base_done = tl >= 0 ? tl_done : INT64_MIN;  // kNever: the node crashed with work left
+      const ChainTail kt = chain_tail(ch, kl);
+      const int64_t base_done = kt.base_done;
 
       WTM(3)
       // 4) the run: publishes jp .. jq-1 up to the earliest pending advert E
@@ -1102,18 +1072,18 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
           e_lane = bnd < e_lane ? bnd : e_lane;
         });
         int64_t E = (int64_t)wave_min_u64((uint64_t)e_lane);
-        if (npend0 > 0) {  // k's own next advert changes its key
+        if (kt.npend > 0) {  // k's own next advert changes its key
           const int64_t hd_done_k = readlane_i64(ch.hd_done, kl);
           const int64_t nxt_k = hd_done_k == kNever ? kNever : hd_done_k + ul_k;
           E = nxt_k < E ? nxt_k : E;
         }
-        if (npend0 == 0) {
+        if (kt.npend == 0) {
           const uint32_t S0 = readlane_u32((uint32_t)cr, jp) / (uint32_t)mips_k;
           const int64_t a0 = t + dl_k;
           int64_t x0 = kNever;
           if (a0 < down_k && base_done != kNever) {
             const int64_t st0 = a0 > base_done ? a0 : base_done;
-            const int64_t d0 = st0 + ticks_of(min(S0, kWideSCap));
+            const int64_t d0 = st0 + ticks_of(min(S0, kChainSCap));
             if (st0 < down_k && d0 < down_k) x0 = d0 + ul_k;
           }
           E = x0 < E ? x0 : E;
@@ -1137,40 +1107,29 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
         S = udiv((uint32_t)cr, div_k);  // double tskTime = requiredMIPS / MIPS (:276)
         a = ca + dl_k;
       }
-      const uint32_t Sd = min(S, kWideSCap);  // tick arithmetic (kWideSCap)
-      const bool one = Lr == 1;               // a single publish needs no wave scans
+      const uint32_t Sd = min(S, kChainSCap);  // tick arithmetic (kChainSCap)
+      const bool one = Lr == 1;                // a single publish needs no wave scans
       // service seconds of the run up to this task: clamped for the ticks (<= 64 * 2^22 < 2^32),
       // exact in 64 bits for the cumulative service (a run with a longer service time is rare)
-      const uint32_t Cs = one ? (in_run ? Sd : 0u) : wave_scan_add_u32(in_run ? Sd : 0u);
+      const uint32_t Cs = run_prefix(in_run, one, Sd);
       uint64_t Cs64 = Cs;
-      if (ballot(in_run && S >= kWideSCap))
+      if (ballot(in_run && S >= kChainSCap))
         Cs64 = one ? (uint64_t)(in_run ? S : 0u) : (uint64_t)wave_scan_add_i64(in_run ? (int64_t)S : 0);
-      const uint64_t C = tl_C + Cs64;  // cumulative assigned service
+      const uint64_t C = kt.tl_C + Cs64;  // cumulative assigned service
       int64_t start = kNever, done = kNever;
       uint32_t status = FOGNET_TASK_LOST;
       if (base_done != kNever) {
-        int64_t X = in_run ? (int64_t)((uint64_t)a - (uint64_t)ticks_of(min(Cs - Sd, kWideSCap))) : INT64_MIN;
-        if (!one) X = wave_scan_max_i64(X);
-        const int64_t dmax = base_done > X ? base_done : X;
+        const int64_t dmax = run_dmax(in_run, one, a, ticks_of(min(Cs - Sd, kChainSCap)), base_done);
         // start = dmax + the run's service before the task, done = dmax + through it; a prefix of
         // 2^22 s or more puts the tick past kMaxTick (kPastRange: lost to a crash, else refused below;
         // a clamped X only over-estimates lanes whose own prefix is past the cap)
-        const int64_t st = Cs - Sd < kWideSCap ? dmax + ticks_of(Cs - Sd) : kPastRange;
-        const int64_t dn = Cs < kWideSCap ? dmax + ticks_of(Cs) : kPastRange;
+        const int64_t st = Cs - Sd < kChainSCap ? dmax + ticks_of(Cs - Sd) : kPastRange;
+        const int64_t dn = Cs < kChainSCap ? dmax + ticks_of(Cs) : kPastRange;
         int64_t prev_done = base_done;
-        uint32_t prev_S = tl_S;
-        if (!one) {
-          const int64_t dn_up = dpp_or_i64<kDppWaveShr1>(0, dn);
-          const uint32_t S_up = dpp_or_u32<kDppWaveShr1>(0u, Sd);
-          if (lane != jp) {
-            prev_done = dn_up;
-            prev_S = S_up;
-          }
-        }
+        uint32_t prev_S = kt.tl_S & 0x7FFFFFFFu;  // (bit 31: the tail was escalated)
+        run_prev(one, lane == jp, dn, Sd, prev_done, prev_S);
         if (in_run && a < down_k) {
-          if (prev_done < a) status = 5u;       // idle: "task assigned" (:282-301)
-          else if (prev_done > a) status = 4u;  // busy: "task queued" (:304-313)
-          else status = dl_k < (int64_t)min(prev_S, kWideSCap) * kTicksPerSecond ? 5u : 4u;  // same-tick completion
+          status = arrival_status(prev_done, min(prev_S, kChainSCap), a, dl_k);
           start = st < down_k ? st : kNever;   // the crash cancels its RELEASERESOURCE
           done = dn < down_k ? dn : kNever;
         }
@@ -1185,7 +1144,7 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
       // task entries: chained in publish order (consecutive task indices)
       const int i = c0 + lane;
       if (in_run) {
-        const int32_t prev = lane == jp ? tl : i - 1;
+        const int32_t prev = lane == jp ? kt.tl : i - 1;
         e[i] = WideEntry{a, done, C, S, prev, lane + 1 < jq ? i + 1 : -1, escalated ? 1 : 0};
         q_on = true;
         q_k = k;
@@ -1207,40 +1166,9 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
       const uint32_t S_f = readlane_u32(S, jp);
       if (lane == kl) {
         WideNode h = ch;
-        const int i0 = c0 + jp, iz = c0 + lz;
-        if (h.npend == 0) {  // the run's first task is the node's head: its advert is the node's next one
-          h.hd = i0;
-          h.hd_done = done_f;
-          h.hd_C = C_f;
-          h.hd_S = S_f;
-          const int64_t x = done_f == kNever ? kNever : done_f + ul_k;
-          const int g = ((int)k / kWave) / kWideGroupSlots;
-          V.nxt[k / kWave] = x;
-          if (x != kNever) {
-            L.g_msk[g * kWave + lane] |= 1u << ((k / kWave) % kWideGroupSlots);
-            gact.set(g, true);
-          }
-          if (x < L.g_nxt[g * kWave + lane]) {
-            L.g_nxt[g * kWave + lane] = x;
-            L.g_j[g * kWave + lane] = (int)k;
-          }
-          if (x < mn) {
-            mn = x;
-            mj = (int)k;
-          }
-        } else if (h.npend >= 2) {
-          e[h.tl].next = i0;
-        }
-        // hd_next after the two-way branch, not in a third arm (DESIGN.md §3.6 "The hd_next
-        // miscompile"): the run's second task on an idle node, its first on a node whose one
-        // pending task is the tail
-        if (h.npend == 1 || (h.npend == 0 && Lr > 1)) h.hd_next = h.npend == 1 ? i0 : i0 + 1;
-        h.tl = iz;
-        h.tl_a = a_z;
-        h.tl_done = done_z;
-        h.tl_C = C_z;
-        h.tl_S = S_z | (escalated ? 0x80000000u : 0u);
-        h.npend += Lr;
+        if (chain_append(h, e, c0 + jp, c0 + lz, Lr, done_f, C_f, S_f, a_z, done_z, C_z,
+                         S_z | (escalated ? 0x80000000u : 0u)))
+          head_advert(k, done_f == kNever ? kNever : done_f + ul_k);
         ch = h;
         max_pend = max(max_pend, (uint32_t)h.npend + pend_k);
         if constexpr (!kPerPublish) {

@@ -1608,6 +1608,105 @@ def test_hier_pending_escalations_spill_to_hbm(ctx, up_s):
     np.testing.assert_array_equal(out.hist.cpu().numpy(), o["hist"].sum(axis=0))
 
 
+def pending_classes(t, node, done, dl, ul, hop, sel):
+    """For each selected task i of the oracle's run, on node k, arriving at a_i = t_i + dl_k + hop_i:
+    of the tasks that reach k before it, lo = those whose advert (done + ul_k) has not reached the
+    broker by a_i and hi = those whose advert has not by t_i.  The device pushes i somewhere in
+    [t_i, a_i], so lo == hi is the number certainly pending on k's record at that push.  Returns
+    how many selected tasks with lo == hi have 0, 1 and >= 2 pending."""
+    a = t + dl[node] + hop
+    idx = np.arange(len(t))
+    cls = []
+    for i in np.flatnonzero(sel):
+        k = node[i]
+        before = (node == k) & ((a < a[i]) | ((a == a[i]) & (idx < i)))
+        adv = done[before] + ul[k]
+        lo, hi = int((adv >= a[i]).sum()), int((adv >= t[i]).sum())
+        if lo == hi:
+            cls.append(min(lo, 2))
+    return [cls.count(c) for c in (0, 1, 2)]
+
+
+def head_next_trace(which, var):
+    """Traces of test_hier_head_next_paths: (trace, threshold, hop).  Two regions: nodes 0..1023 and
+    node 1024 alone; every node 1000 MIPS, 1-ms links, first advert at 2 ms."""
+    MS, S = 10**9, 10**12
+    N = 1025
+    if which == "escalated":  # var: the hop
+        pubs = [(50 * MS, 10000, 1), (50 * MS + 1, 10000, 1), (50 * MS + 2, 10000, 1),
+                (11 * S, 2000, 1), (11 * S + S // 2, 2000, 1), (12 * S, 2000, 1), (12 * S + S // 2, 2000, 1),
+                (25 * S, 3000, 1), (25 * S + 5, 1000, 0), (26 * S, 1000, 1),
+                (45 * S, 1000, 0), (46 * S, 1000, 1)]
+        thr, up = 0, var
+    else:  # test_wide_head_next_paths' bursts; var: every fifth publish in region 1
+        pubs = []
+        for b, (n, gap_s) in enumerate(((1, 3), (2, 5), (3, 7), (6, 11), (2, 2), (1, 1))):
+            t0 = 50 * MS + sum((3, 5, 7, 11, 2, 1)[:b]) * S + b * MS
+            for q in range(n):
+                pubs.append((t0 + q, (1 + (q + b) % 3) * 1000, 1 if var and len(pubs) % 5 == 4 else 0))
+        thr, up = 10**6, 10 * MS
+    tr = dict(arrive=np.array([p[0] for p in pubs], np.int64)[None], req=np.array([p[1] for p in pubs], np.int32)[None],
+              region=np.array([p[2] for p in pubs], np.int32)[None], mips=np.full(N, 1000, np.int32),
+              dl=np.full(N, MS, np.int64), ul=np.full(N, MS, np.int64), init=np.full(N, 2 * MS, np.int64))
+    return tr, thr, up
+
+
+@pytest.mark.parametrize("which,var,regions,resume", [
+    ("escalated", 10**10, "0", "1"), ("escalated", 10**10, "1", "1"), ("escalated", 10**10, "1", "0"),
+    ("escalated", 2 * 10**12, "0", "1"), ("escalated", 2 * 10**12, "1", "1"), ("escalated", 2 * 10**12, "1", "0"),
+    ("direct", False, "only", "1"), ("direct", False, "0", "1"),
+    ("direct", True, "only", "1"), ("direct", True, "0", "1")])
+def test_hier_head_next_paths(ctx, monkeypatch, which, var, regions, resume):
+    """The paths that set a node record's hd_next (test_wide_head_next_paths), for
+    the two other places that append to a node's chain: the deferred push of an escalated task in
+    the sequential wide kernel, and the region kernel's runs.
+
+    "escalated": node 1024 (a region of its own) takes three publishes and then advertises 20 s
+    busy, so the region's next publishes escalate to node 0, one after the other, before node 0
+    has advertised; the direct publish at 25 s + 5 overtakes the escalated one of 25 s.  The
+    escalated pushes land on a node with no, one and two or more pending tasks (1 / 2 / 2 of them
+    at a 10-ms hop, 1 / 1 / 2 at a 2-s hop), sequentially (FOGNET_HIER_REGIONS=0), resumed after
+    the region pass stopped before publish 3 (the wide kernel continues from the handed-over
+    chains) and restarted (FOGNET_HIER_RESUME=0).
+
+    "direct": the bursts of test_wide_head_next_paths, never escalating, with every publish in
+    region 0 or every fifth one in region 1; the region pass finishes the replication itself
+    (FOGNET_HIER_REGIONS=only) and the sequential kernel (=0) gives the same.  Runs land on a node
+    with no, one and two or more pending tasks (6 / 4 / 5 and 8 / 4 / 3 tasks).
+
+    Per-task outputs, the record's bytes and the histogram equal the oracle's."""
+    tr, thr, up = head_next_trace(which, var)
+    o = ol.run_batch(tr["arrive"], tr["req"], tr["mips"], tr["dl"], tr["ul"], tr["init"], hist=True,
+                     policy=ol.POLICY_EXT_HIER, region=tr["region"], hier_threshold_s=thr, hier_up_tick=up)
+    assert o["stats"]["status"][0] == 0
+    esc = o["node"][0] // _abi.HIER_REGION_NODES != tr["region"][0]
+    if which == "escalated":
+        assert o["node"][0].tolist() == [1024, 1024, 1024, 0, 0, 0, 0, 0, 0, 0, 0, 1024]
+        assert esc.tolist() == [False] * 3 + [True] * 5 + [False, True, False, False]
+    else:
+        assert not esc.any()
+        assert int(o["stats"]["max_pending"][0]) >= 3
+    # the guard: the oracle's run reaches every arm of the chain append
+    classes = pending_classes(tr["arrive"][0], o["node"][0], o["done"][0], tr["dl"], tr["ul"], np.where(esc, up, 0),
+                              esc if which == "escalated" else ~esc)
+    assert min(classes) >= 1, classes
+    monkeypatch.setenv("FOGNET_HIER_REGIONS", regions)
+    monkeypatch.setenv("FOGNET_HIER_RESUME", resume)
+    before = ctx.hier_path_stats()
+    out = fa.run_batch(ctx, fa.as_device_trace(tr, torch.device("cuda", ctx.device)), policy="EXT_HIER",
+                       hier_threshold_s=thr, hier_up_tick=up, hist=True)
+    torch.cuda.synchronize()
+    st = out.rep_stats()
+    assert st["status"][0] == 0
+    if regions == "only":
+        assert ctx.hier_path_stats() == (before[0] + 1, before[1])
+    g = dict(node=out.node.cpu().numpy(), status=out.status.cpu().numpy(), start=out.start_tick.cpu().numpy(),
+             done=out.done_tick.cpu().numpy(), stats=st)
+    assert_parity(tr, g, o)
+    assert st.tobytes() == o["stats"].tobytes()
+    np.testing.assert_array_equal(out.hist.cpu().numpy(), o["hist"].sum(axis=0))
+
+
 @pytest.mark.parametrize("mode", ["only", "0"])
 def test_c5_ext_hier_as_named(ctx, monkeypatch, mode):
     """Config C5 as BASELINE.json configs[4] names it, in the bench's settings:
