@@ -763,6 +763,10 @@ int fognet_run_batch(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_out*
 int fognet_user_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out, const int64_t* user_ul,
                           const int64_t* user_dl, int32_t user_per_task, fognet_user_stats* user_stats, void* stream) {
   if (!c || !out) return FOGNET_ERR_ARG;
+  if (in && in->policy == FOGNET_POLICY_EXT_HIER)
+    return fail(c, FOGNET_ERR_UNSUPPORTED,
+                "user signals under EXT_HIER: the acks of an escalated task leave its node hier_up_tick later, and "
+                "the per-task outputs do not say which tasks were escalated");
   fognet::ReplayArgs a;
   int rc = prepare(c, in, &a);
   if (rc) return rc;

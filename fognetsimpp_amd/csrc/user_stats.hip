@@ -10,7 +10,9 @@
 // simtime_t values, fognet_hip.h "Reference signal values"), created = the
 // publish's send time = its broker arrival - the user uplink.  Acks carry no
 // state back into the decision loop, so every signal is a closed form of the
-// replay outputs; tests/oracle_lib restates them as real FES events.
+// replay outputs; tests/oracle_lib restates them as real FES events.  The closed
+// form needs every node ack to leave at t + dl_k: REF_V3 and EXT_LAT (capi.hip
+// refuses EXT_HIER, whose escalated tasks reach their node hier_up_tick later).
 // Memory-bound: one 256-thread workgroup per replication streams its tasks.
 #include "replay_common.h"
 
@@ -61,7 +63,12 @@ __global__ __launch_bounds__(kUserThreads) void user_stats_kernel(ReplayArgs A, 
   const int r = blockIdx.x;
   const size_t tbase = (size_t)r * (size_t)A.T;
   const size_t nbase = (size_t)r * (size_t)A.node_stride;
-  const int n = (int)A.out_stats[r].n_tasks;  // decided tasks (written by the replay)
+  // a failed replication: the empty record, nothing of its rows or links is read (its rows are
+  // undefined, fognet_hip.h "Buffers"; fognet_node_stats_dev's rule)
+  const int32_t rep_status = A.out_stats[r].status;
+  const bool ok = rep_status == FOGNET_OK || rep_status == FOGNET_REF_ABORTED;
+  const int64_t n64 = A.out_stats[r].n_tasks;  // decided tasks (written by the replay)
+  const int n = !ok || n64 < 0 ? 0 : (int)(n64 > A.T ? A.T : n64);
   Mom m[kSignals];
   for (int s = 0; s < kSignals; ++s) mom_init(m[s]);
   for (int i = threadIdx.x; i < n; i += kUserThreads) {

@@ -95,6 +95,10 @@ class Context:
             msg = self._lib.fognet_last_error(self._h).decode()
             raise FognetError(rc, f"{what}: {msg}" if what else msg)
 
+    def last_error(self) -> str:
+        """The message of this context's last failed call (fognet_last_error)."""
+        return self._lib.fognet_last_error(self._h).decode()
+
     def sync(self):
         self.check(self._lib.fognet_sync(self._h), "sync")
 
@@ -221,6 +225,7 @@ class BatchResult:
     stats: torch.Tensor       # [R * sizeof(fognet_rep_stats)] uint8 (device)
     node_energy: torch.Tensor | None = None  # [R, N] float64 (power model only)
     hist: torch.Tensor | None = None         # [2, 64] int64 job histogram (queueTime, response), added to
+    policy: int | None = None                # fognet_policy of the run_batch that filled these buffers (None: not run)
 
     def rep_stats(self) -> np.ndarray:
         return self.stats.cpu().numpy().view(_abi.REP_STATS_DTYPE)
@@ -313,6 +318,7 @@ def run_batch(ctx: Context, trace: dict, out: BatchResult | None = None, ring_ca
     fn = {"all": ctx._lib.fognet_run_batch_dev, "replay": ctx._lib.fognet_replay_dev,
           "stats": ctx._lib.fognet_rep_stats_dev}[stage]
     ctx.check(fn(ctx.handle, C.byref(bi), C.byref(bo), s), f"run_batch[{stage}]")
+    out.policy = pol  # what user_stats goes by when it is given no policy
     return out
 
 
@@ -358,13 +364,20 @@ def run_generated(ctx: Context, seed: int, R: int, T: int, N: int, mean_gap_tick
 
 
 def user_stats(ctx: Context, trace: dict, out: BatchResult, user_ul, user_dl,
-               res: torch.Tensor | None = None) -> np.ndarray:
+               res: torch.Tensor | None = None, policy: str | int | None = None) -> np.ndarray:
     """User-side signals (fognet_user_stats_dev) of a finished replay: broker
     ``delay`` and mqttApp2's ``latency`` / ``latencyH1`` / ``taskTime`` as exact
     tick moments per replication (USER_STATS_DTYPE [R]).  ``user_ul`` /
     ``user_dl``: the publishing user's links, [R] (one user per replication)
     or [R, T] (per task), host arrays or device tensors.  ``res``: the device
-    buffer the records are written to (uint8, R * sizeof(fognet_user_stats))."""
+    buffer the records are written to (uint8, R * sizeof(fognet_user_stats)).
+    ``policy``: the replay's; None takes the one :func:`run_batch` recorded on
+    ``out`` (REF_V3 for buffers it did not fill).  "REF_V3" and "EXT_LAT";
+    EXT_HIER is refused (FOGNET_ERR_UNSUPPORTED, nothing is written): the acks
+    of an escalated task leave its node ``hier_up_tick`` later, and the
+    per-task outputs do not say which tasks were escalated.  A failed
+    replication (status other than FOGNET_OK / FOGNET_REF_ABORTED) gets the
+    empty record."""
     arrive = trace["arrive"]
     R, T = arrive.shape
     dev = arrive.device
@@ -384,9 +397,13 @@ def user_stats(ctx: Context, trace: dict, out: BatchResult, user_ul, user_dl,
         res = torch.zeros(nres, dtype=torch.uint8, device=dev)
     else:
         _check_bytes(res, nres, dev, "res")
-    bi = _abi.BatchIn(R, T, N, _abi.FOGNET_POLICY_REF_V3, N if mips.dim() == 2 else 0, 0,
+    if policy is None:
+        policy = out.policy if out.policy is not None else _abi.FOGNET_POLICY_REF_V3
+    pol = POLICIES[policy] if isinstance(policy, str) else int(policy)
+    hier = pol == _abi.FOGNET_POLICY_EXT_HIER
+    bi = _abi.BatchIn(R, T, N, pol, N if mips.dim() == 2 else 0, 0,
                       _ptr(arrive), _ptr(trace["req"]), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
-                      _ptr(trace["init"]), None, None)
+                      _ptr(trace["init"]), None, None, None, _ptr(trace.get("region")) if hier else None)
     bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick),
                        _ptr(out.stats), None, None)
     ctx.check(ctx._lib.fognet_user_stats_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(uu), _ptr(ud), per_task,

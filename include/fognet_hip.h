@@ -303,8 +303,9 @@ typedef struct fognet_batch_out {
  *     maxima (last_tick too) INT64_MIN, abort_tick = INT64_MAX, abort_task = -1.
  *     (fognet_replay_dev alone writes only the four fields named at its declaration;
  *     fognet_rep_stats_dev completes the record.)  Likewise fognet_v2_stats (every count 0
- *     for a replication refused before its first event) and fognet_user_stats (the
- *     count == 0 values of fognet_moments for a replication with n_tasks = 0).
+ *     for a replication refused before its first event).  fognet_user_stats_dev reads
+ *     nothing of a failed replication's rows, wherever it failed: its fognet_user_stats
+ *     holds the count == 0 values of fognet_moments in all four signals.
  *   The per-node records (fognet_node_stats_dev's [R][N], fognet_reduce_node_stats_dev's [N])
  *     obey every sentence above: 8-B alignment, nothing outside [R][N] / [N] touched, no
  *     initialisation needed; a failed replication's row is N empty records. */
@@ -499,7 +500,18 @@ int fognet_run_batch(fognet_ctx *ctx, const fognet_batch_in *in, fognet_batch_ou
  * node parameters) and `out` (node, status, done_tick, stats) plus the
  * publishing users' links user_ul_tick (user -> broker) and user_dl_tick
  * (broker -> user): [R] (one user per replication, user_per_task = 0) or
- * [R][T] (per task, = 1).  Writes user_stats [R] (device). */
+ * [R][T] (per task, = 1).  Writes user_stats [R] (device): record r covers
+ * replication r's first stats[r].n_tasks publishes; a failed replication (status
+ * other than FOGNET_OK / FOGNET_REF_ABORTED) gets the count == 0 record in all four
+ * signals, and none of its per-task rows or link entries is read (a
+ * FOGNET_REF_ABORTED one keeps its full record).  The signals are a closed form of
+ * the per-task outputs that holds where every node ack leaves at arrive_tick +
+ * dl_k: FOGNET_POLICY_REF_V3 and FOGNET_POLICY_EXT_LAT, with or without down_tick.
+ * Refused: FOGNET_POLICY_EXT_HIER (FOGNET_ERR_UNSUPPORTED, before anything else is
+ * checked and with nothing written: an escalated task reaches its node
+ * hier_up_tick later, so do its acks, and the per-task outputs do not say which
+ * tasks were escalated).  The policy is the caller's word: EXT_HIER outputs passed
+ * under another policy are computed as if no task had been escalated. */
 int fognet_user_stats_dev(fognet_ctx *ctx, const fognet_batch_in *in, const fognet_batch_out *out,
                           const int64_t *user_ul_tick, const int64_t *user_dl_tick, int32_t user_per_task,
                           fognet_user_stats *user_stats, void *hip_stream);

@@ -38,7 +38,8 @@ import oracle_lib as ol
 import tracegen as tg
 from fognetsimpp_amd import _abi
 from guarded import Arena
-from test_parity_gpu import (V2_FIELDS, assert_parity, assert_user_parity, job_from_reps, v2_random, with_crashes)
+from test_parity_gpu import (V2_FIELDS, assert_parity, job_from_reps, v2_random, with_crashes)
+from user_stats_ref import assert_user_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -106,6 +107,8 @@ CASES = [
     dict(id="user-per-replication", kind="user", per_task=False, failed=False),
     dict(id="user-per-task", kind="user", per_task=True, failed=False),
     dict(id="user-per-task-failed", kind="user", per_task=True, failed=True),
+    # refused at publish 65 of 130 (out of order), after its first decisions: its rows are undefined and unread
+    dict(id="user-per-task-failed-mid", kind="user", per_task=True, failed="mid", T=130),
     *[dict(id=f"decide-v3-m{m}xn{n}", kind="decide3", m=m, n=n) for m in (1, 63, 65, 257) for n in (1, 65)],
     *[dict(id=f"decide-v2-m{m}xn{n}", kind="decide2", m=m, n=n) for m in (1, 63, 65, 257) for n in (1, 65)],
     dict(id="tracegen-3x5x65", kind="tracegen", R=3, N=5, T=65), dict(id="tracegen-2x65x191", kind="tracegen", R=2, N=65, T=191),
@@ -167,9 +170,11 @@ def generated_inputs(c):
 
 def user_inputs(c):
     if c["id"] not in _cache:
-        R, N, T = 3, 64, 65
+        R, N, T = 3, 64, c.get("T", 65)
         tr = {k: v.copy() for k, v in tg.make_batch(0x5EED0003, R, N, T, rho=0.9).items()}
-        if c["failed"]:
+        if c["failed"] == "mid":
+            tr["arrive"][1, T // 2] = tr["arrive"][1, T // 2 - 1] - 1
+        elif c["failed"]:
             tr["mips"][1, 0] = 0
         rng = np.random.default_rng(31)
         shape = (R, T) if c["per_task"] else (R,)
@@ -435,6 +440,8 @@ def check_against_oracle(ctx, case, g):
         failed = is_failed(g["stats"])
         assert list(failed) == [False, bool(case["failed"]), False]
         assert_user_parity(g["user"][~failed], o["user"][~failed])
+        if case["failed"] == "mid":  # it had decided publishes when it was refused
+            assert 0 < int(g["stats"]["n_tasks"][1]) <= case["T"] // 2
         for r in np.flatnonzero(failed):  # an empty record: fognet_moments' count == 0 values
             for n in ol.USER_SIGNALS:
                 m = g["user"][r][n]

@@ -10,6 +10,7 @@ import oracle_lib as ol
 import tracegen as tg
 from fognetsimpp_amd import _abi
 from test_oracle import c1_trace, check_fifo_invariants, hier_kat
+from user_stats_ref import assert_user_parity
 
 pytestmark = pytest.mark.gpu
 TPS = 10**12
@@ -1035,12 +1036,6 @@ def test_c5_large_topology_sample(ctx):
 # ------------------------------------------------------------------ user-side signals (ack relay)
 # fognet_user_stats_dev (closed form over the replay outputs) against the
 # oracle's event-level restatement (acks as FES events relayed by the broker).
-
-def assert_user_parity(g_user, o_user):
-    for n in ol.USER_SIGNALS:
-        for f in ("count", "min_raw", "max_raw", "sum_lo", "sum_hi", "sq_lo", "sq_hi", "sq_top", "overflow"):
-            np.testing.assert_array_equal(g_user[n][f], o_user[n][f], err_msg=f"{n}.{f}")
-
 
 @pytest.mark.parametrize("kind", ["one_user", "per_task", "tie_heavy", "wide"])
 def test_user_stats_match_oracle(ctx, kind):
