@@ -136,7 +136,7 @@ class BatchIn(C.Structure):
 class BatchOut(C.Structure):
     _fields_ = [("node", C.c_void_p), ("status", C.c_void_p), ("start_tick", C.c_void_p),
                 ("done_tick", C.c_void_p), ("stats", C.c_void_p), ("node_energy_j", C.c_void_p),
-                ("hist", C.c_void_p)]
+                ("hist", C.c_void_p), ("escalated", C.c_void_p)]
 
 
 class GenParams(C.Structure):

@@ -354,6 +354,8 @@ int stage(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_out* out, void*
   const bool stats_only = n_null == 4 && a.T > 0;
   if (stats_only && which != 3)
     return fail(c, FOGNET_ERR_UNSUPPORTED, "statistics-only replays run through fognet_run_batch_dev");
+  if (stats_only && out->escalated)
+    return fail(c, FOGNET_ERR_ARG, "escalated is a per-task output: a statistics-only out has none");
   if (a.R == 0) return FOGNET_OK;
   rc = set_device(c);
   if (rc) return rc;
@@ -366,6 +368,13 @@ int stage(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_out* out, void*
   a.hist = out->hist;
   if (a.out_energy && !a.p_busy) return fail(c, FOGNET_ERR_ARG, "node_energy_j needs the power model (p_busy_w/p_idle_w)");
   const hipStream_t s = (hipStream_t)stream;
+  // the escalation flags: written by the EXT_HIER replay paths; no other policy escalates
+  if (a.policy == FOGNET_POLICY_EXT_HIER) {
+    a.out_esc = out->escalated;
+  } else if (out->escalated && (which & 1) && a.T > 0) {
+    const hipError_t e = hipMemsetAsync(out->escalated, 0, (size_t)a.R * (size_t)a.T, s);
+    if (e != hipSuccess) return hip_fail(c, e, "escalated clear");
+  }
   if (use_wide(a.N) || a.down || a.policy == FOGNET_POLICY_EXT_HIER) {  // (regions: the wide kernel's groups)
     // crashes are only modelled by the wide kernel; it accumulates the statistics while it replays, so the
     // statistics-only stage has nothing left to do
@@ -619,7 +628,7 @@ int fognet_run_generated_dev(fognet_ctx* c, const fognet_gen_params* p, int64_t 
     return fail(c, FOGNET_ERR_ARG, "generated replay: the trace and node-parameter arrays must be NULL (generated)");
   // (EXT_HIER: each publish's region from the mobility model of fa.mobility_regions, computed in the
   // kernel, replication by replication on the sequential wide kernel)
-  if (out->node || out->status || out->start_tick || out->done_tick)
+  if (out->node || out->status || out->start_tick || out->done_tick || out->escalated)
     return fail(c, FOGNET_ERR_ARG, "generated replay: statistics only (per-task arrays must be NULL)");
   if (!out->stats) return fail(c, FOGNET_ERR_ARG, "stats output is required (per-replication status)");
   if (r0 < 0 || p->req_lo < 0 || p->req_hi < p->req_lo) return fail(c, FOGNET_ERR_ARG, "bad r0 or req range");
@@ -693,7 +702,7 @@ int fognet_run_batch(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_out*
   // before the launch, dst copied out after it; hist is both, because it is added to.
   struct Buf { const void* src; void* dst; size_t bytes; bool present; void* dev; };
   enum { kRegion, kArrive, kReq, kMips, kDl, kUl, kInit, kPBusy, kPIdle, kDown,
-         kNode, kStatus, kStart, kDone, kStats, kEnergy, kHist, kBufs };
+         kNode, kStatus, kStart, kDone, kStats, kEnergy, kHist, kEsc, kBufs };
   const bool rg = in->policy == FOGNET_POLICY_EXT_HIER && in->region != nullptr;
   Buf b[kBufs] = {
       {in->region, nullptr, RT * 4, rg},
@@ -713,6 +722,7 @@ int fognet_run_batch(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_out*
       {nullptr, out->stats, R * sizeof(fognet_rep_stats), true},
       {nullptr, out->node_energy_j, R * N * 8, out->node_energy_j != nullptr},
       {out->hist, out->hist, HB, out->hist != nullptr},
+      {nullptr, out->escalated, RT * 1, out->escalated != nullptr},
   };
   rc = [&]() -> int {
     hipError_t e;
@@ -737,7 +747,7 @@ int fognet_run_batch(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_out*
     din.down_tick = (const int64_t*)b[kDown].dev;
     fognet_batch_out dout = {(int32_t*)b[kNode].dev, (uint8_t*)b[kStatus].dev, (int64_t*)b[kStart].dev,
                              (int64_t*)b[kDone].dev, (fognet_rep_stats*)b[kStats].dev, (double*)b[kEnergy].dev,
-                             (int64_t*)b[kHist].dev};
+                             (int64_t*)b[kHist].dev, (uint8_t*)b[kEsc].dev};
     const int rc_run = fognet_run_batch_dev(c, &din, &dout, c->stream);
     if (rc_run) return rc_run;
     for (Buf& x : b)
@@ -763,10 +773,10 @@ int fognet_run_batch(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_out*
 int fognet_user_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out, const int64_t* user_ul,
                           const int64_t* user_dl, int32_t user_per_task, fognet_user_stats* user_stats, void* stream) {
   if (!c || !out) return FOGNET_ERR_ARG;
-  if (in && in->policy == FOGNET_POLICY_EXT_HIER)
+  if (in && in->policy == FOGNET_POLICY_EXT_HIER && !out->escalated)
     return fail(c, FOGNET_ERR_UNSUPPORTED,
                 "user signals under EXT_HIER: the acks of an escalated task leave its node hier_up_tick later, and "
-                "the per-task outputs do not say which tasks were escalated");
+                "the per-task outputs do not say which tasks were escalated (replay with fognet_batch_out.escalated)");
   fognet::ReplayArgs a;
   int rc = prepare(c, in, &a);
   if (rc) return rc;
@@ -780,6 +790,7 @@ int fognet_user_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet
   a.out_status = out->status;
   a.out_done = out->done_tick;
   a.out_stats = out->stats;
+  if (a.policy == FOGNET_POLICY_EXT_HIER) a.out_esc = out->escalated;  // (not read under the other policies)
   hipError_t e = fognet::launch_user_stats(a, user_ul, user_dl, user_per_task, user_stats, (hipStream_t)stream);
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "user stats launch");
 }
@@ -787,10 +798,10 @@ int fognet_user_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet
 int fognet_node_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out,
                           fognet_node_stats* node_stats, void* stream) {
   if (!c || !out) return FOGNET_ERR_ARG;
-  if (in && in->policy == FOGNET_POLICY_EXT_HIER)
+  if (in && in->policy == FOGNET_POLICY_EXT_HIER && !out->escalated)
     return fail(c, FOGNET_ERR_UNSUPPORTED,
                 "node statistics under EXT_HIER: an escalated task reaches its node hier_up_tick later, and the "
-                "per-task outputs do not say which tasks were escalated");
+                "per-task outputs do not say which tasks were escalated (replay with fognet_batch_out.escalated)");
   fognet::ReplayArgs a;
   int rc = prepare(c, in, &a);
   if (rc) return rc;
@@ -806,6 +817,7 @@ int fognet_node_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet
   a.out_start = out->start_tick;
   a.out_done = out->done_tick;
   a.out_stats = out->stats;
+  if (a.policy == FOGNET_POLICY_EXT_HIER) a.out_esc = out->escalated;  // (not read under the other policies)
   // FOGNET_NODE_STATS=hbm: the accumulators are the caller's records for every N (the layout of
   // N > node_stats_lds_max()), so small tests run both layouts on the same traces
   const hipError_t e = fognet::launch_node_stats(a, node_stats, env_is("FOGNET_NODE_STATS", "hbm"), (hipStream_t)stream);

@@ -285,6 +285,10 @@ struct ReplayArgs {
   uint32_t* board;
   // FOGNET_FLAG_REF_ABORT: a replication with an abort point gets status FOGNET_REF_ABORTED
   int32_t ref_abort;
+  // fognet_batch_out.escalated, [R][T] (nullable: every store of it is skipped).  Written by the
+  // EXT_HIER paths only (replay_wide.hip, replay_region.hip); the other policies' launches clear it
+  // with a memset (capi.hip).  The statistics passes read it under EXT_HIER (the hop, hier_up).
+  uint8_t* out_esc;
 };
 
 // Generated-mode launch: 3 waves per SIMD, 4 SIMDs per CU (replay_gen_kernel)

@@ -4,8 +4,9 @@
 // counts, service seconds and responses.
 //
 // The pass is a reduction keyed by node over the replay's per-task arrays (33 B per
-// task).  One workgroup per replication streams them coalesced, 64 tasks per wavefront
-// and step.  The accumulators are one fognet_node_stats per node: in LDS up to
+// task; 34 under EXT_HIER, whose escalated tasks are enqueued a hop later).  One
+// workgroup per replication streams them coalesced, 64 tasks per wavefront and
+// step.  The accumulators are one fognet_node_stats per node: in LDS up to
 // kNodeLdsMax nodes (copied to the caller's records at the end), above that the caller's
 // records themselves, set to the empty record first.  Every update is an integer atomic:
 // sums take their carries from the value the atomic add returns, extrema are integer
@@ -153,10 +154,13 @@ struct TaskRow {
   int64_t t, start, done;
   int32_t req, node;
   uint32_t status;
+  uint32_t esc;  // EXT_HIER: the parent took the decision (the task reached its node a hop later)
 };
 
+// (A.out_esc: the replay's escalation flags, passed by capi.hip under EXT_HIER only)
 __device__ __forceinline__ TaskRow load_task(const ReplayArgs& A, size_t o) {
-  return TaskRow{A.arrive[o], A.out_start[o], A.out_done[o], A.req[o], A.out_node[o], (uint32_t)A.out_status[o]};
+  return TaskRow{A.arrive[o], A.out_start[o], A.out_done[o], A.req[o], A.out_node[o], (uint32_t)A.out_status[o],
+                 A.out_esc ? (uint32_t)A.out_esc[o] : 0u};
 }
 
 // kLds: the accumulators, the nodes' downlinks and their MIPS dividers live in LDS
@@ -219,7 +223,7 @@ __global__ __launch_bounds__(kNodeThreads) void node_stats_kernel(ReplayArgs A, 
       }
       if (cur.status == 4u && cur.start >= 0) {  // queueTime emission (ComputeBrokerApp3.cc:238)
         int64_t raw;
-        if (qtime_raw(cur.start, cur.t + dl_k, raw)) {
+        if (qtime_raw(cur.start, cur.t + dl_k + (cur.esc ? A.hier_up : 0), raw)) {
           p.cnt += (uint64_t)1 << kCQn;
           p.qmin = p.qmax = raw;
           add_moment_signed(p.qs_lo, p.qs_hi, p.qq_lo, p.qq_hi, p.qq_top, raw);

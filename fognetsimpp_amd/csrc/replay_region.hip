@@ -763,6 +763,7 @@ __global__ __launch_bounds__(kFinThreads) void region_finish_kernel(ReplayArgs A
           A.out_status[o] = (uint8_t)stt[u];
           A.out_start[o] = st0[u];
           A.out_done[o] = dn[u];
+          if (A.out_esc) A.out_esc[o] = 0;  // (the region pass ends before the first escalated publish)
           const int64_t resp = dn[u] - t[u];
           add_moment(b.rs_lo, b.rs_hi, b.rq_lo, b.rq_hi, (uint64_t)resp);
           b.rmin = min(b.rmin, resp);

@@ -313,7 +313,7 @@ struct GenNodes {
   uint64_t* dv;
 };
 
-template <int POL, bool BIG>
+template <int POL, bool BIG, bool ESC>
 __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int wr, WideEntry* E, WideNode* ND,
                                                 int64_t* VN, uint32_t* VB, int64_t* VW, GenNodes GN, int32_t* OV,
                                                 unsigned char* GX, const RegionWs& RW, unsigned char* w_lds);
@@ -322,30 +322,34 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
 // the replications the register kernel handed over, taken in turn by the
 // workgroups (workspace slot = blockIdx.x); every workgroup leaves when the
 // list (complete before this launch, stream order) is exhausted.
-template <int POL, bool BIG>
+// ESC (EXT_HIER): the per-task escalation flags are written (A.out_esc is set).  A template flag, not a
+// test of the pointer: the instantiation without it is the kernel as it was (measured at the saturating
+// C5 recipe, the test alone cost 0.3 ms of 72: the kernel has no scalar register to keep the pointer in).
+template <int POL, bool BIG, bool ESC = false>
 __global__ __launch_bounds__(64) void replay_wide_kernel(ReplayArgs A, WideEntry* E, WideNode* ND, int64_t* VN,
                                                          uint32_t* VB, int64_t* VW, GenNodes GN, int32_t* OV,
                                                          unsigned char* GX, RegionWs RW) {
   extern __shared__ __align__(16) unsigned char w_lds[];
   if (A.wide_list == nullptr) {
-    replay_wide_rep<POL, BIG>(A, blockIdx.x, blockIdx.x, E, ND, VN, VB, VW, GN, OV, GX, RW, w_lds);
+    replay_wide_rep<POL, BIG, ESC>(A, blockIdx.x, blockIdx.x, E, ND, VN, VB, VW, GN, OV, GX, RW, w_lds);
     return;
   }
   const int n = *A.wide_count;
   for (int i = blockIdx.x; i < n; i += gridDim.x) {
-    replay_wide_rep<POL, BIG>(A, A.wide_list[i], blockIdx.x, E, ND, VN, VB, VW, GN, OV, GX, RW, w_lds);
+    replay_wide_rep<POL, BIG, ESC>(A, A.wide_list[i], blockIdx.x, E, ND, VN, VB, VW, GN, OV, GX, RW, w_lds);
     __syncthreads();  // LDS reuse by the next replication
   }
 }
 
 // Replication r with workspace slot wr.
-template <int POL, bool BIG>
+template <int POL, bool BIG, bool ESC>
 __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int wr, WideEntry* E, WideNode* ND,
                                                 int64_t* VN, uint32_t* VB, int64_t* VW, GenNodes GN, int32_t* OV,
                                                 unsigned char* GX, const RegionWs& RW, unsigned char* w_lds) {
   constexpr bool kExt = POL == FOGNET_POLICY_EXT_LAT;
   constexpr bool kHier = POL == FOGNET_POLICY_EXT_HIER;
   static_assert(!(BIG && kHier), "EXT_HIER keeps its regions (groups) in LDS");
+  static_assert(!ESC || kHier, "only EXT_HIER escalates");
   constexpr bool kPerPublish = kExt || kHier;  // the decision depends on the publish itself
   const int lane = threadIdx.x;
   const int T = A.T, N = A.N;
@@ -662,6 +666,7 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
       A.out_status[o] = (uint8_t)status;
       A.out_start[o] = start == kNever ? -1 : start;
       A.out_done[o] = done == kNever ? -1 : done;
+      if constexpr (ESC) A.out_esc[o] = 1;  // (every pushed pending task was the parent's decision)
     }
     // its statistics: staged, accumulated 64 tasks at a time (drain_stats), like the chunk's
     if (n_sq == kWave) drain_stats();
@@ -1193,6 +1198,8 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
       A.out_status[o] = (uint8_t)q_status;
       A.out_start[o] = q_start == kNever ? -1 : q_start;
       A.out_done[o] = q_done == kNever ? -1 : q_done;
+      // EXT_HIER: the chunk's lanes are its direct tasks (an escalated one is stored by push_one)
+      if constexpr (ESC) A.out_esc[o] = 0;
     }
     if (q_on) {
       if (q_done != kNever) {
@@ -1279,14 +1286,14 @@ __device__ __forceinline__ void replay_wide_rep(const ReplayArgs& A, int r, int 
   }
 }
 
-template <int POL, bool BIG>
+template <int POL, bool BIG, bool ESC = false>
 void launch_wide_pol(const ReplayArgs& a, int32_t slots, WideEntry* e, WideNode* nd, int64_t* vn, uint32_t* vb,
                      int64_t* vw, GenNodes gn, int32_t* ov, unsigned char* gx, const RegionWs& rw, size_t lds,
                      hipStream_t s) {
   if (lds > 65536)  // above the default dynamic-LDS limit (N > ~51,000 nodes; gfx950 has 160 KiB per CU)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&replay_wide_kernel<POL, BIG>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&replay_wide_kernel<POL, BIG, ESC>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((replay_wide_kernel<POL, BIG>), dim3(slots), dim3(kWave), lds, s, a, e, nd, vn, vb, vw, gn, ov,
+  hipLaunchKernelGGL((replay_wide_kernel<POL, BIG, ESC>), dim3(slots), dim3(kWave), lds, s, a, e, nd, vn, vb, vw, gn, ov,
                      gx, rw);
 }
 
@@ -1343,7 +1350,10 @@ hipError_t launch_replay_wide(const ReplayArgs& a, void* workspace, int32_t slot
     else
       launch_wide_pol<FOGNET_POLICY_EXT_LAT, false>(a, slots, e, nd, vn, vb, vw, gn, ov, gx, rw, lds, s);
   } else if (a.policy == FOGNET_POLICY_EXT_HIER) {
-    launch_wide_pol<FOGNET_POLICY_EXT_HIER, false>(a, slots, e, nd, vn, vb, vw, gn, ov, gx, rw, lds, s);
+    if (a.out_esc && !a.no_task_out)
+      launch_wide_pol<FOGNET_POLICY_EXT_HIER, false, true>(a, slots, e, nd, vn, vb, vw, gn, ov, gx, rw, lds, s);
+    else
+      launch_wide_pol<FOGNET_POLICY_EXT_HIER, false>(a, slots, e, nd, vn, vb, vw, gn, ov, gx, rw, lds, s);
   } else if (big) {
     launch_wide_pol<FOGNET_POLICY_REF_V3, true>(a, slots, e, nd, vn, vb, vw, gn, ov, gx, rw, lds, s);
   } else {

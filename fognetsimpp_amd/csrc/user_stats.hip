@@ -11,8 +11,10 @@
 // publish's send time = its broker arrival - the user uplink.  Acks carry no
 // state back into the decision loop, so every signal is a closed form of the
 // replay outputs; tests/oracle_lib restates them as real FES events.  The closed
-// form needs every node ack to leave at t + dl_k: REF_V3 and EXT_LAT (capi.hip
-// refuses EXT_HIER, whose escalated tasks reach their node hier_up_tick later).
+// form needs the tick every node ack leaves at: t + dl_k under REF_V3 and EXT_LAT;
+// under EXT_HIER an escalated task reaches its node hier_up_tick later, so the
+// replay's escalation flags (fognet_batch_out.escalated) add the hop to that term
+// (capi.hip refuses EXT_HIER without them).
 // Memory-bound: one 256-thread workgroup per replication streams its tasks.
 #include "replay_common.h"
 
@@ -69,6 +71,8 @@ __global__ __launch_bounds__(kUserThreads) void user_stats_kernel(ReplayArgs A, 
   const bool ok = rep_status == FOGNET_OK || rep_status == FOGNET_REF_ABORTED;
   const int64_t n64 = A.out_stats[r].n_tasks;  // decided tasks (written by the replay)
   const int n = !ok || n64 < 0 ? 0 : (int)(n64 > A.T ? A.T : n64);
+  // EXT_HIER: the replay's per-task escalation flags (capi.hip passes them under that policy only)
+  const uint8_t* const esc = A.out_esc;
   Mom m[kSignals];
   for (int s = 0; s < kSignals; ++s) mom_init(m[s]);
   for (int i = threadIdx.x; i < n; i += kUserThreads) {
@@ -83,7 +87,9 @@ __global__ __launch_bounds__(kUserThreads) void user_stats_kernel(ReplayArgs A, 
     const int64_t relay = A.ul[nbase + k] + ud;  // node -> broker -> user
     mom_add(m[0], uu);                            // delay: at the broker (:143), a simtime_t (s)
     mom_add_ms(m[2], t + ud - created);           // broker pubAck status 4 -> latencyH1
-    const int64_t at_arrival = t + A.dl[nbase + k] + relay - created;  // node ack sent at the task's arrival
+    // node ack sent at the task's arrival: t + dl_k, the parent's hop later for an escalated task
+    const int64_t hop = esc && esc[o] ? A.hier_up : 0;
+    const int64_t at_arrival = t + A.dl[nbase + k] + hop + relay - created;
     if (st == 5u)
       mom_add_ms(m[1], at_arrival);  // "task assigned" -> latency
     else if (st == 4u)

@@ -226,15 +226,21 @@ class BatchResult:
     node_energy: torch.Tensor | None = None  # [R, N] float64 (power model only)
     hist: torch.Tensor | None = None         # [2, 64] int64 job histogram (queueTime, response), added to
     policy: int | None = None                # fognet_policy of the run_batch that filled these buffers (None: not run)
+    escalated: torch.Tensor | None = None    # [R, T] uint8, EXT_HIER: 1 where the parent broker took the decision
+    hier_up_tick: int = 0                    # the hop of that run_batch (EXT_HIER; what user_stats / node_stats add)
 
     def rep_stats(self) -> np.ndarray:
         return self.stats.cpu().numpy().view(_abi.REP_STATS_DTYPE)
 
 
 def allocate_outputs(R: int, T: int, device, N: int | None = None, energy: bool = False,
-                     hist: bool = False, per_task: bool = True) -> BatchResult:
+                     hist: bool = False, per_task: bool = True, escalated: bool = False) -> BatchResult:
     """Output buffers; ``per_task=False``: statistics only (no per-task arrays:
-    the replay writes nothing per task, fognet_batch_out)."""
+    the replay writes nothing per task, fognet_batch_out).  ``escalated``: also
+    the per-task escalation flags (fognet_batch_out.escalated), which
+    :func:`user_stats` and :func:`node_stats` need under EXT_HIER."""
+    if escalated and not per_task:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "escalated is a per-task output: not with per_task=False")
     mk = (lambda shape, dt: torch.empty(shape, dtype=dt, device=device)) if per_task else (lambda shape, dt: None)
     return BatchResult(
         node=mk((R, T), torch.int32),
@@ -244,6 +250,7 @@ def allocate_outputs(R: int, T: int, device, N: int | None = None, energy: bool 
         stats=torch.zeros(R * _abi.REP_STATS_DTYPE.itemsize, dtype=torch.uint8, device=device),
         node_energy=torch.zeros((R, N), dtype=torch.float64, device=device) if energy else None,
         hist=torch.zeros((_abi.HIST_METRICS, _abi.HIST_BINS), dtype=torch.int64, device=device) if hist else None,
+        escalated=torch.empty((R, T), dtype=torch.uint8, device=device) if escalated else None,
     )
 
 
@@ -266,7 +273,8 @@ def as_device_trace(trace: dict, device) -> dict:
 
 def run_batch(ctx: Context, trace: dict, out: BatchResult | None = None, ring_capacity: int = 0,
               stream=None, stage: str = "all", policy: str | int = "REF_V3", hist: bool = False,
-              hier_threshold_s: int = 60, hier_up_tick: int = 20 * 10**9, ref_abort: bool = False) -> BatchResult:
+              hier_threshold_s: int = 60, hier_up_tick: int = 20 * 10**9, ref_abort: bool = False,
+              escalated: bool = False) -> BatchResult:
     """Enqueue R trace replays (fognet_run_batch_dev) on the current stream.
 
     ``trace``: device tensors arrive/req [R, T], node params mips/dl/ul/init
@@ -283,7 +291,10 @@ def run_batch(ctx: Context, trace: dict, out: BatchResult | None = None, ring_ca
     histogram when ``out`` is None.  ``ref_abort`` (FOGNET_FLAG_REF_ABORT): a
     replication the reference run would end at a queueTime overflow gets status
     FOGNET_REF_ABORTED (its abort point, ``abort_tick``/``abort_task``, is in
-    every record either way).
+    every record either way).  ``escalated``: allocate the per-task escalation
+    flags when ``out`` is None (``out.escalated`` [R, T] uint8: 1 where the
+    parent broker took the decision under EXT_HIER, all 0 under the other
+    policies); an ``out`` that carries the array gets it filled either way.
     """
     arrive, req = trace["arrive"], trace["req"]
     R, T = arrive.shape
@@ -303,7 +314,10 @@ def run_batch(ctx: Context, trace: dict, out: BatchResult | None = None, ring_ca
                             or out.stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize):
         raise FognetError(_abi.FOGNET_ERR_ARG, "output buffers too small for the trace")
     if out is None:
-        out = allocate_outputs(R, T, arrive.device, N=N, energy=energy, hist=hist)
+        out = allocate_outputs(R, T, arrive.device, N=N, energy=energy, hist=hist, escalated=escalated)
+    if out.escalated is not None and (out.escalated.dtype != torch.uint8 or tuple(out.escalated.shape) != (R, T)
+                                      or out.escalated.stride(-1) != 1 or (R > 1 and out.escalated.stride(0) != T)):
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"out.escalated: a row-contiguous uint8 [{R}, {T}] tensor")
     region = trace.get("region")
     if pol == _abi.FOGNET_POLICY_EXT_HIER and (region is None or tuple(region.shape) != (R, T)):
         raise FognetError(_abi.FOGNET_ERR_ARG, "EXT_HIER needs trace['region'] of shape [R, T]")
@@ -313,12 +327,13 @@ def run_batch(ctx: Context, trace: dict, out: BatchResult | None = None, ring_ca
                       _ptr(region), int(hier_up_tick), int(hier_threshold_s),
                       _abi.FLAG_REF_ABORT if ref_abort else 0)
     bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick),
-                       _ptr(out.stats), _ptr(out.node_energy), _ptr(out.hist))
+                       _ptr(out.stats), _ptr(out.node_energy), _ptr(out.hist), _ptr(out.escalated))
     s = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr(arrive.device)
     fn = {"all": ctx._lib.fognet_run_batch_dev, "replay": ctx._lib.fognet_replay_dev,
           "stats": ctx._lib.fognet_rep_stats_dev}[stage]
     ctx.check(fn(ctx.handle, C.byref(bi), C.byref(bo), s), f"run_batch[{stage}]")
     out.policy = pol  # what user_stats goes by when it is given no policy
+    out.hier_up_tick = int(hier_up_tick) if pol == _abi.FOGNET_POLICY_EXT_HIER else 0
     return out
 
 
@@ -363,8 +378,14 @@ def run_generated(ctx: Context, seed: int, R: int, T: int, N: int, mean_gap_tick
     return out
 
 
+def _hier_up(out: BatchResult, hier_up_tick) -> int:
+    """The EXT_HIER hop a statistics pass adds to escalated tasks: the caller's, else the replay's."""
+    return int(out.hier_up_tick if hier_up_tick is None else hier_up_tick)
+
+
 def user_stats(ctx: Context, trace: dict, out: BatchResult, user_ul, user_dl,
-               res: torch.Tensor | None = None, policy: str | int | None = None) -> np.ndarray:
+               res: torch.Tensor | None = None, policy: str | int | None = None,
+               hier_up_tick: int | None = None) -> np.ndarray:
     """User-side signals (fognet_user_stats_dev) of a finished replay: broker
     ``delay`` and mqttApp2's ``latency`` / ``latencyH1`` / ``taskTime`` as exact
     tick moments per replication (USER_STATS_DTYPE [R]).  ``user_ul`` /
@@ -373,9 +394,12 @@ def user_stats(ctx: Context, trace: dict, out: BatchResult, user_ul, user_dl,
     buffer the records are written to (uint8, R * sizeof(fognet_user_stats)).
     ``policy``: the replay's; None takes the one :func:`run_batch` recorded on
     ``out`` (REF_V3 for buffers it did not fill).  "REF_V3" and "EXT_LAT";
-    EXT_HIER is refused (FOGNET_ERR_UNSUPPORTED, nothing is written): the acks
-    of an escalated task leave its node ``hier_up_tick`` later, and the
-    per-task outputs do not say which tasks were escalated.  A failed
+    "EXT_HIER" when ``out.escalated`` holds the replay's escalation flags
+    (``run_batch(..., escalated=True)``): the node ack of an escalated task
+    leaves ``hier_up_tick`` later (None: the hop run_batch recorded on
+    ``out``).  Without the flags EXT_HIER is refused (FOGNET_ERR_UNSUPPORTED,
+    nothing is written): the other per-task outputs do not say which tasks
+    were escalated.  A failed
     replication (status other than FOGNET_OK / FOGNET_REF_ABORTED) gets the
     empty record."""
     arrive = trace["arrive"]
@@ -403,22 +427,26 @@ def user_stats(ctx: Context, trace: dict, out: BatchResult, user_ul, user_dl,
     hier = pol == _abi.FOGNET_POLICY_EXT_HIER
     bi = _abi.BatchIn(R, T, N, pol, N if mips.dim() == 2 else 0, 0,
                       _ptr(arrive), _ptr(trace["req"]), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
-                      _ptr(trace["init"]), None, None, None, _ptr(trace.get("region")) if hier else None)
+                      _ptr(trace["init"]), None, None, None, _ptr(trace.get("region")) if hier else None,
+                      _hier_up(out, hier_up_tick) if hier else 0)
     bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick),
-                       _ptr(out.stats), None, None)
+                       _ptr(out.stats), None, None, _ptr(out.escalated) if hier else None)
     ctx.check(ctx._lib.fognet_user_stats_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(uu), _ptr(ud), per_task,
                                              _ptr(res), _stream_ptr(dev)), "user_stats")
     return res[:nres].cpu().numpy().view(_abi.USER_STATS_DTYPE)
 
 
 def node_stats(ctx: Context, trace: dict, out: BatchResult, policy: str | int = "REF_V3",
-               res: torch.Tensor | None = None) -> torch.Tensor:
+               res: torch.Tensor | None = None, hier_up_tick: int | None = None) -> torch.Tensor:
     """Per-node statistics (fognet_node_stats_dev) of a finished replay on the
     current stream: what the reference records per ComputeBroker module.
     Returns the device buffer of the records, uint8 [R, N * sizeof(fognet_node_stats)]
     (``.cpu().numpy().view(_abi.NODE_STATS_DTYPE)`` gives [R, N] records); ``res``:
     write into this buffer instead of a new one.  ``policy``: the replay's
-    ("REF_V3" or "EXT_LAT"; EXT_HIER is refused, FOGNET_ERR_UNSUPPORTED)."""
+    ("REF_V3" or "EXT_LAT"; "EXT_HIER" when ``out.escalated`` holds the replay's
+    escalation flags, ``run_batch(..., escalated=True)`` -- an escalated task is
+    enqueued ``hier_up_tick`` later (None: the hop run_batch recorded on ``out``) --
+    and refused without them, FOGNET_ERR_UNSUPPORTED)."""
     arrive = trace["arrive"]
     R, T = arrive.shape
     dev = arrive.device
@@ -433,9 +461,10 @@ def node_stats(ctx: Context, trace: dict, out: BatchResult, policy: str | int = 
     hier = pol == _abi.FOGNET_POLICY_EXT_HIER
     bi = _abi.BatchIn(R, T, N, pol, N if mips.dim() == 2 else 0, 0,
                       _ptr(arrive), _ptr(trace["req"]), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
-                      _ptr(trace["init"]), None, None, _ptr(trace.get("down")), _ptr(trace.get("region")) if hier else None)
+                      _ptr(trace["init"]), None, None, _ptr(trace.get("down")), _ptr(trace.get("region")) if hier else None,
+                      _hier_up(out, hier_up_tick) if hier else 0)
     bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick),
-                       _ptr(out.stats), None, None)
+                       _ptr(out.stats), None, None, _ptr(out.escalated) if hier else None)
     ctx.check(ctx._lib.fognet_node_stats_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(res), _stream_ptr(dev)),
               "node_stats")
     return res[:nres].view(R, N * _abi.NODE_STATS_DTYPE.itemsize)

@@ -112,7 +112,10 @@ typedef enum fognet_policy {
                                    (the node FIFO takes any length, ComputeBrokerApp3.cc:305-309).
                                    A replication that fails (status != OK) leaves the per-task
                                    outputs of escalated tasks still in flight at the error
-                                   unwritten, like every task after the error.                */
+                                   unwritten, like every task after the error.  Which tasks the
+                                   parent decided is the optional output fognet_batch_out.escalated;
+                                   fognet_user_stats_dev and fognet_node_stats_dev need it under
+                                   this policy (they add the hop to those tasks' arrival).     */
 } fognet_policy;
 
 /* Region size of FOGNET_POLICY_EXT_HIER (node r * 1024 .. r * 1024 + 1023 form region r). */
@@ -282,12 +285,21 @@ typedef struct fognet_batch_out {
     double *node_energy_j;    /* [R][N] per-node energy (nullable; needs the power model)         */
     int64_t *hist;            /* [FOGNET_HIST_METRICS][FOGNET_HIST_BINS] job histogram, ADDED to
                                  (the caller zeroes it; nullable)                                 */
+    uint8_t *escalated;       /* [R][T] nullable (needs the four per-task arrays: FOGNET_ERR_ARG with a
+                                 statistics-only out).  FOGNET_POLICY_EXT_HIER: 1 for a decided task
+                                 whose decision the parent broker took (its region's minimum above
+                                 hier_threshold_s), whether or not the chosen node lies in the
+                                 publish's own region and also when that node has crashed (status
+                                 9); else 0.  Other policies: filled with 0.  Last member: a caller
+                                 that zeroes the struct or initialises only the members above
+                                 passes NULL and sees no change.                                  */
 } fognet_batch_out;
 
 /* Buffers.  What every *_dev entry point asks of, and leaves in, the caller's arrays
  * (tests/test_buffer_contract_gpu.py holds the library to each sentence):
  *   Alignment.  Every pointer needs only the natural alignment of its element type
- *     (8 B for int64 / double / the record structs, 4 B for int32, 1 B for status).
+ *     (8 B for int64 / double / the record structs, 4 B for int32, 1 B for status and
+ *     escalated).
  *   Bounds.  Nothing outside [R][T] / [R|1][N] / [R] / [m] / hist is read or written,
  *     whatever T % 64, R % 4 (the v2 wavefronts) or R % 4096 (the reduction) are.
  *   Initialisation.  No output needs initialising, and none depends on what it held
@@ -308,7 +320,9 @@ typedef struct fognet_batch_out {
  *     holds the count == 0 values of fognet_moments in all four signals.
  *   The per-node records (fognet_node_stats_dev's [R][N], fognet_reduce_node_stats_dev's [N])
  *     obey every sentence above: 8-B alignment, nothing outside [R][N] / [N] touched, no
- *     initialisation needed; a failed replication's row is N empty records. */
+ *     initialisation needed; a failed replication's row is N empty records.
+ *   escalated likewise: 1-B alignment, nothing outside [R][T] touched, no initialisation
+ *     needed; a failed replication's row is undefined, like its other per-task rows. */
 
 /* count / min / max / exact signed 128-bit sum and 192-bit sum of squares of a
  * signal's raw emitted values (min_raw = INT64_MAX, max_raw = INT64_MIN when
@@ -354,8 +368,9 @@ typedef struct fognet_node_stats {
     int64_t busy_s;      /* service seconds req / MIPS_k (int division) of its COMPLETED tasks */
     int64_t last_tick;   /* latest completion tick on this node; INT64_MIN if none             */
     fognet_moments queue;/* this module's queueTime emissions, raw values ("Reference signal
-                            values"): status-4 tasks that started, enqueued at arrive + dl_k,
-                            started at start_tick; overflow = emissions the reference throws on */
+                            values"): status-4 tasks that started, enqueued at arrive + dl_k
+                            (+ hier_up_tick for an escalated task), started at start_tick;
+                            overflow = emissions the reference throws on                       */
     fognet_moments resp; /* done_tick - arrive_tick (ticks) of its completed tasks; overflow 0  */
 } fognet_node_stats;     /* 192 B, 8-B aligned */
 
@@ -507,11 +522,15 @@ int fognet_run_batch(fognet_ctx *ctx, const fognet_batch_in *in, fognet_batch_ou
  * FOGNET_REF_ABORTED one keeps its full record).  The signals are a closed form of
  * the per-task outputs that holds where every node ack leaves at arrive_tick +
  * dl_k: FOGNET_POLICY_REF_V3 and FOGNET_POLICY_EXT_LAT, with or without down_tick.
- * Refused: FOGNET_POLICY_EXT_HIER (FOGNET_ERR_UNSUPPORTED, before anything else is
- * checked and with nothing written: an escalated task reaches its node
- * hier_up_tick later, so do its acks, and the per-task outputs do not say which
- * tasks were escalated).  The policy is the caller's word: EXT_HIER outputs passed
- * under another policy are computed as if no task had been escalated. */
+ * FOGNET_POLICY_EXT_HIER with out->escalated (the replay's flags): the node ack of task
+ * i leaves at arrive_tick + dl_k + in->hier_up_tick * escalated[i] (the hop; the broker's
+ * own pubAck, delay and taskTime, which goes by done_tick, do not move).  Refused:
+ * FOGNET_POLICY_EXT_HIER with out->escalated NULL (FOGNET_ERR_UNSUPPORTED, before
+ * anything else is checked and with nothing written: an escalated task reaches its
+ * node hier_up_tick later, so do its acks, and the other per-task outputs do not say
+ * which tasks were escalated).  The policy is the caller's word: EXT_HIER outputs passed
+ * under another policy are computed as if no task had been escalated (escalated is
+ * not read then). */
 int fognet_user_stats_dev(fognet_ctx *ctx, const fognet_batch_in *in, const fognet_batch_out *out,
                           const int64_t *user_ul_tick, const int64_t *user_dl_tick, int32_t user_per_task,
                           fognet_user_stats *user_stats, void *hip_stream);
@@ -523,10 +542,13 @@ int fognet_user_stats_dev(fognet_ctx *ctx, const fognet_batch_in *in, const fogn
  * of replication r's nodes over its first stats[r].n_tasks publishes; a failed
  * replication (status other than FOGNET_OK / FOGNET_REF_ABORTED) gets N empty records
  * and nothing of its per-task rows is read.  FOGNET_POLICY_REF_V3 and
- * FOGNET_POLICY_EXT_LAT, with or without down_tick.  Refused: FOGNET_POLICY_EXT_HIER
- * (FOGNET_ERR_UNSUPPORTED: an escalated task reaches its node hier_up_tick later, and the
- * per-task outputs do not say which tasks were escalated), a statistics-only `out`
- * (FOGNET_ERR_ARG) and a NULL node_stats with R * N > 0 (FOGNET_ERR_ARG).
+ * FOGNET_POLICY_EXT_LAT, with or without down_tick; FOGNET_POLICY_EXT_HIER with
+ * out->escalated (the replay's flags): task i is enqueued at arrive_tick + dl_k +
+ * in->hier_up_tick * escalated[i].  Refused: FOGNET_POLICY_EXT_HIER with out->escalated
+ * NULL (FOGNET_ERR_UNSUPPORTED: an escalated task reaches its node hier_up_tick later, and
+ * the other per-task outputs do not say which tasks were escalated), a statistics-only
+ * `out` (FOGNET_ERR_ARG) and a NULL node_stats with R * N > 0 (FOGNET_ERR_ARG).  Under the
+ * other policies escalated is not read.
  * FOGNET_NODE_STATS=hbm (environment, testing): the accumulators are the caller's
  * records for every N, as they are above 256 nodes; the results are identical. */
 int fognet_node_stats_dev(fognet_ctx *ctx, const fognet_batch_in *in, const fognet_batch_out *out,

@@ -8,7 +8,12 @@ traces generated on the device as bench.py does.  Each pass: warm-up launches, t
 timed repeats between events on the stream; the median is reported, with the achieved
 GB/s over the bytes the pass must move (33 B per task + its records).
 
-  python tools/node_stats_timing.py [--out profiles/node_stats_timing.txt] [--reps N]
+``--shapes c5hier,c5sat``: C5 under EXT_HIER (bench.py's light recipe, where no region
+escalates, and its saturating recipe, T = 32,768, where every replication does): the replay
+without and with the per-task escalation flags (fognet_batch_out.escalated, one more byte
+per task), then the user-signal and per-node passes that read them (34 B per task).
+
+  python tools/node_stats_timing.py [--out profiles/node_stats_timing.txt] [--reps N] [--shapes c3,c5flat]
 """
 from __future__ import annotations
 
@@ -24,7 +29,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fognetsimpp_amd as fa  # noqa: E402
 from fognetsimpp_amd import _abi  # noqa: E402
 
-SHAPES = {"c3": (4096, 100_000, 256), "c5flat": (1024, 10_000, 10_000)}
+SHAPES = {"c3": (4096, 100_000, 256), "c5flat": (1024, 10_000, 10_000),
+          "c5hier": (1024, 10_000, 10_000), "c5sat": (1024, 32_768, 10_000)}
+HIER = dict(policy="EXT_HIER", hier_threshold_s=60, hier_up_tick=20 * 10**9)  # bench.py's defaults
 
 
 def timed(fn, warmup: int, reps: int) -> list[float]:
@@ -42,6 +49,41 @@ def timed(fn, warmup: int, reps: int) -> list[float]:
     return ms
 
 
+def time_hier(ctx, dev, name: str, R: int, T: int, N: int, args) -> list[str]:
+    """C5 under EXT_HIER: the replay without / with the escalation flags and the two passes that read them."""
+    if name == "c5sat":
+        tr = fa.as_device_trace(fa.saturating_trace(0x5EED0005, R, T, N), dev)
+    else:
+        mg, sc = fa.c5_params(np.arange(R), N)
+        d = fa.generate_trace(ctx, 0x5EED0005, R, T, N, mg, sc)
+        tr = {k: v for k, v in d.items() if not k.startswith("_")}
+        tr["region"] = fa.mobility_regions(tr["arrive"], N)
+    plain = fa.allocate_outputs(R, T, dev)
+    out = fa.allocate_outputs(R, T, dev, escalated=True)
+    fa.run_batch(ctx, tr, out=out, **HIER)
+    torch.cuda.synchronize()
+    ok = int((out.rep_stats()["status"] == 0).sum())
+    n_esc = int(out.escalated.sum(dtype=torch.int64))
+    uu = torch.full((R,), 2 * 10**9, dtype=torch.int64, device=dev)
+    ud = torch.full((R,), 3 * 10**9, dtype=torch.int64, device=dev)
+    users = torch.empty(R * _abi.USER_STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    nodes = torch.empty(R * N * _abi.NODE_STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    rec_bytes = R * N * _abi.NODE_STATS_DTYPE.itemsize
+    passes = {
+        "replay": (lambda: fa.run_batch(ctx, tr, out=plain, **HIER), None),
+        "replay+escalated": (lambda: fa.run_batch(ctx, tr, out=out, **HIER), None),
+        "user_stats": (lambda: fa.user_stats(ctx, tr, out, uu, ud, res=users), 22 * R * T),
+        "node_stats": (lambda: fa.node_stats(ctx, tr, out, policy="EXT_HIER", res=nodes), 34 * R * T + rec_bytes),
+    }
+    lines = [f"{name} R={R} T={T} N={N} EXT_HIER ok={ok} escalated tasks={n_esc}"]
+    for pname, (fn, nbytes) in passes.items():
+        ms = timed(fn, args.warmup, args.reps)
+        med = statistics.median(ms)
+        rate = f", {nbytes / 1e6:.1f} MB, {nbytes / med / 1e6:.1f} GB/s" if nbytes else ""
+        lines.append(f"{name} {pname}: median {med:.3f} ms (min {min(ms):.3f}, max {max(ms):.3f}){rate}")
+    return lines
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -54,6 +96,9 @@ def main() -> int:
     lines = [f"device: {torch.cuda.get_device_name(0)}; median of {args.reps} timed launches after {args.warmup} warm-up"]
     for name in args.shapes.split(","):
         R, T, N = SHAPES[name]
+        if name in ("c5hier", "c5sat"):
+            lines += time_hier(ctx, dev, name, R, T, N, args)
+            continue
         mg, sc = (fa.c5_params if name == "c5flat" else fa.sweep_params)(np.arange(R), N)
         d = fa.generate_trace(ctx, 0x5EED0003, R, T, N, mg, sc)
         tr = {k: v for k, v in d.items() if not k.startswith("_")}
