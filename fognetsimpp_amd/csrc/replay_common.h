@@ -284,6 +284,46 @@ __device__ __forceinline__ void add_moment_signed(uint64_t& slo, uint64_t& shi, 
   add192(qlo, qhi, qtop, sl, sh, 0u);
 }
 
+// Sum of squares as three running partial sums (the packed statistics pass):
+// with v = h 2^32 + l, sum v^2 = 2^64 sum h^2 + 2^33 sum h l + sum l^2 exactly,
+// so a task costs three 32 x 32 + 64 multiply-adds instead of assembling its
+// 128-bit square, and the wide sum is formed once per lane after the loop.
+// Exactness: a product of two 32-bit factors is below 2^64, so one 64-bit
+// accumulation wraps at most once, and the multiply-add's carry-out says so;
+// c_* count the wraps.  A lane accumulates at most ceil(T / 64) <= 2^25 values
+// (T < 2^31), so a 32-bit count cannot wrap itself, and sum = acc + 2^64 c holds
+// for every 64-bit v: no bound on the ticks is needed.
+struct SqParts {
+  uint64_t ll, hl, hh;
+  uint32_t c_ll, c_hl, c_hh;
+};
+
+// acc += x * y, wraps += the carry out of that 64-bit addition.  (v_mad_u64_u32
+// delivers the carry in VCC and the add-with-carry takes it from there: the
+// VOP3B/VOP2 carry pair the compiler itself emits for every 64-bit addition,
+// which needs no wait state between the two.)
+__device__ __forceinline__ void mad_wrap(uint64_t& acc, uint32_t& wraps, uint32_t x, uint32_t y) {
+  asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc"
+      : "+v"(acc), "+v"(wraps)
+      : "v"(x), "v"(y)
+      : "vcc");
+}
+
+__device__ __forceinline__ void sq_parts_add(SqParts& p, uint64_t v) {
+  const uint32_t l = (uint32_t)v, h = (uint32_t)(v >> 32);
+  mad_wrap(p.ll, p.c_ll, l, l);
+  mad_wrap(p.hl, p.c_hl, h, l);
+  mad_wrap(p.hh, p.c_hh, h, h);
+}
+
+// (lo, hi, top) += the partial sums' total, modulo 2^192:
+// (ll + 2^64 c_ll) + 2^33 (hl + 2^64 c_hl) + 2^64 (hh + 2^64 c_hh)
+__device__ __forceinline__ void sq_parts_fold(const SqParts& p, uint64_t& lo, uint64_t& hi, uint64_t& top) {
+  add192(lo, hi, top, p.ll, p.c_ll, 0u);
+  add192(lo, hi, top, p.hl << 33, (p.hl >> 31) | ((uint64_t)p.c_hl << 33), (uint64_t)p.c_hl >> 31);
+  add192(lo, hi, top, 0u, p.hh, p.c_hh);
+}
+
 // one queueTime emission of a task enqueued at tick a, started at tick start;
 // false: the emission overflows (the reference throws there: its abort point)
 __device__ __forceinline__ bool acc_qtime(uint64_t& qs_lo, uint64_t& qs_hi, uint64_t& qq_lo, uint64_t& qq_hi,
@@ -531,6 +571,7 @@ __device__ __forceinline__ void stats_accumulate_packed(const ReplayArgs& A, siz
   const int64_t* const arrive = A.arrive + tbase;
   const int64_t* const done = A.out_done + tbase;
   int32_t* const word = A.out_node + tbase;
+  SqParts rsq = {}, qsq = {};  // squares of the response and of |queueTime|: folded into `a` after the loop
   auto rows = [&](const PackedRows<UNROLL>& s, uint32_t ib) {  // ib < n
     const uint32_t lim = n - 1u - ib;
 #pragma unroll
@@ -546,15 +587,25 @@ __device__ __forceinline__ void stats_accumulate_packed(const ReplayArgs& A, siz
           if (energy) atomicAdd(&s_busy[k], (unsigned long long)S);
           a.last = max(a.last, s.dn[u]);
         }
-        add_moment(a.rs_lo, a.rs_hi, a.rq_lo, a.rq_hi, (uint64_t)resp);
+        add128(a.rs_lo, a.rs_hi, (uint64_t)resp, 0u);
+        sq_parts_add(rsq, (uint64_t)resp);
         a.rmin = min(a.rmin, resp);
         a.rmax = max(a.rmax, resp);
         if (hist) atomicAdd(&s_hist[FOGNET_HIST_BINS + hist_bin(resp)], 1u);
         if (status == 4u) {  // queueTime emission (ComputeBrokerApp3.cc:238), enqueued at its arrival
           a.n4 += 1u;
-          if (!acc_qtime(a.qs_lo, a.qs_hi, a.qq_lo, a.qq_hi, a.qq_top, a.qmin, a.qmax, a.nqt, a.nqo, start,
-                         s.t[u] + dl_of((int)k), hist ? s_hist : nullptr))
+          int64_t raw;
+          if (qtime_raw(start, s.t[u] + dl_of((int)k), raw)) {  // (acc_qtime, the squares apart)
+            add128(a.qs_lo, a.qs_hi, (uint64_t)raw, raw < 0 ? ~(uint64_t)0 : 0u);  // two's complement
+            sq_parts_add(qsq, raw < 0 ? (uint64_t)0 - (uint64_t)raw : (uint64_t)raw);
+            a.qmin = min(a.qmin, raw);
+            a.qmax = max(a.qmax, raw);
+            a.nqt += 1u;
+            if (hist) atomicAdd(&s_hist[hist_bin_raw(raw)], 1u);
+          } else {  // the reference throws there: its abort point
+            a.nqo += 1u;
             abort_min(ab_tick[lane], ab_task[lane], start, (int32_t)(ib + o));
+          }
         } else {
           a.n5 += 1u;
         }
@@ -574,6 +625,9 @@ __device__ __forceinline__ void stats_accumulate_packed(const ReplayArgs& A, siz
     ib += kStep;
     if (ib >= n) break;
   }
+  uint64_t top = 0u;  // (the response's sum of squares is a 128-bit field: modulo 2^128, as add_moment)
+  sq_parts_fold(rsq, a.rq_lo, a.rq_hi, top);
+  sq_parts_fold(qsq, a.qq_lo, a.qq_hi, a.qq_top);
 }
 
 // ---------------------------------------------------------------- wide-record advert
