@@ -207,6 +207,11 @@ SIGNATURES = {
     "fognet_reduce_node_stats_dev": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, P]),
     "fognet_node_stats_init": (None, [C.POINTER(NodeStats)]),
     "fognet_node_stats_merge": (None, [C.POINTER(NodeStats), C.POINTER(NodeStats)]),
+    "fognet_per_user_stats_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P, C.c_int32, C.c_int32,
+                                            P, P, P, P, P]),
+    "fognet_reduce_user_stats_dev": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, P]),
+    "fognet_user_stats_init": (None, [C.POINTER(UserStats)]),
+    "fognet_user_stats_merge": (None, [C.POINTER(UserStats), C.POINTER(UserStats)]),
     "fognet_job_stats_init": (None, [C.POINTER(JobStats)]),
     "fognet_job_stats_merge": (None, [C.POINTER(JobStats), C.POINTER(JobStats)]),
     "fognet_job_stats_add_rep": (None, [C.POINTER(JobStats), C.POINTER(RepStats)]),
@@ -227,6 +232,7 @@ SIGNATURES = {
     "fognet_trace_read": (C.c_int, [C.c_char_p, C.POINTER(BatchIn), P]),
     "fognet_write_sca": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(JobStats), P]),
     "fognet_write_sca_nodes": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int]),
+    "fognet_write_sca_users": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int]),
     "fognet_write_vec": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P, P, P, P, P, P]),
     "fognet_gen_trace_mqtt": (C.c_int, [C.c_uint32, C.c_int32, P, P, P, P, C.c_int64, C.c_int32, C.c_int32,
                                         C.c_int32, P, P, P, C.POINTER(C.c_int32)]),

@@ -836,6 +836,52 @@ int fognet_reduce_node_stats_dev(fognet_ctx* c, const fognet_node_stats* node_st
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "node reduce launch");
 }
 
+int fognet_per_user_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out,
+                              const int32_t* user_of, int32_t U, int32_t link_stride, const int64_t* user_ul,
+                              const int64_t* user_dl, fognet_user_stats* per_user, int64_t* n_unassigned, void* stream) {
+  if (!c || !out) return FOGNET_ERR_ARG;
+  if (in && in->policy == FOGNET_POLICY_EXT_HIER && !out->escalated)
+    return fail(c, FOGNET_ERR_UNSUPPORTED,
+                "per-user signals under EXT_HIER: the acks of an escalated task leave its node hier_up_tick later, "
+                "and the per-task outputs do not say which tasks were escalated (replay with "
+                "fognet_batch_out.escalated)");
+  fognet::ReplayArgs a;
+  int rc = prepare(c, in, &a);
+  if (rc) return rc;
+  if (U < 0) return fail(c, FOGNET_ERR_ARG, "negative U");
+  if (link_stride != 0 && link_stride != U) return fail(c, FOGNET_ERR_ARG, "link_stride must be 0 or U");
+  if (a.R == 0) return FOGNET_OK;
+  if (!out->stats) return fail(c, FOGNET_ERR_ARG, "null stats");
+  if (a.T > 0 && (!out->node || !out->status || !out->done_tick))
+    return fail(c, FOGNET_ERR_ARG, "per-user signals need the per-task outputs (a statistics-only out has none)");
+  if (a.T > 0 && !user_of && (U > 0 || n_unassigned)) return fail(c, FOGNET_ERR_ARG, "null user_of");
+  if (U > 0 && (!per_user || !user_ul || !user_dl)) return fail(c, FOGNET_ERR_ARG, "null per_user or user links");
+  rc = set_device(c);
+  if (rc) return rc;
+  a.out_node = out->node;
+  a.out_status = out->status;
+  a.out_done = out->done_tick;
+  a.out_stats = out->stats;
+  if (a.policy == FOGNET_POLICY_EXT_HIER) a.out_esc = out->escalated;  // (not read under the other policies)
+  // FOGNET_USER_STATS=hbm: the accumulators are the caller's records for every U (the layout of
+  // U > per_user_stats_lds_max()), so small tests run both layouts on the same traces
+  const hipError_t e = fognet::launch_per_user_stats(a, user_of, U, link_stride, user_ul, user_dl, per_user, n_unassigned,
+                                                     env_is("FOGNET_USER_STATS", "hbm"), (hipStream_t)stream);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "per-user stats launch");
+}
+
+int fognet_reduce_user_stats_dev(fognet_ctx* c, const fognet_user_stats* user_stats, const fognet_rep_stats* stats,
+                                 int32_t R, int32_t U, fognet_user_stats* out, void* stream) {
+  if (!c) return FOGNET_ERR_ARG;
+  if (R < 0 || U < 0) return fail(c, FOGNET_ERR_ARG, "negative R/U");
+  if (U == 0) return FOGNET_OK;
+  if (!out || (R > 0 && (!user_stats || !stats))) return fail(c, FOGNET_ERR_ARG, "null pointer");
+  const int rc = set_device(c);
+  if (rc) return rc;
+  const hipError_t e = fognet::launch_reduce_user_stats(user_stats, stats, R, U, out, (hipStream_t)stream);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "user reduce launch");
+}
+
 int fognet_run_v2_dev(fognet_ctx* c, const fognet_v2_in* in, fognet_v2_out* out, void* stream) {
   if (!c || !in || !out) return FOGNET_ERR_ARG;
   if (in->R < 0 || in->T < 0 || in->N < 0) return fail(c, FOGNET_ERR_ARG, "negative R/T/N");
@@ -994,6 +1040,22 @@ void fognet_node_stats_merge(fognet_node_stats* a, const fognet_node_stats* b) {
   if (b->last_tick > a->last_tick) a->last_tick = b->last_tick;
   moments_merge_host(&a->queue, &b->queue);
   moments_merge_host(&a->resp, &b->resp);
+}
+
+void fognet_user_stats_init(fognet_user_stats* s) {
+  if (!s) return;
+  moments_init_host(&s->delay);
+  moments_init_host(&s->latency);
+  moments_init_host(&s->latencyH1);
+  moments_init_host(&s->taskTime);
+}
+
+void fognet_user_stats_merge(fognet_user_stats* a, const fognet_user_stats* b) {
+  if (!a || !b) return;
+  moments_merge_host(&a->delay, &b->delay);
+  moments_merge_host(&a->latency, &b->latency);
+  moments_merge_host(&a->latencyH1, &b->latencyH1);
+  moments_merge_host(&a->taskTime, &b->taskTime);
 }
 
 int fognet_gen_trace_dev(fognet_ctx* c, const fognet_gen_params* p, int64_t r0, int32_t R, int32_t T, int32_t N,

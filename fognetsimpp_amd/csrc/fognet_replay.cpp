@@ -334,7 +334,7 @@ struct Options {
   int nodes = 0, reps = 1, device = 0, ring = 0;
   uint32_t seed = 1;
   int64_t dl = kMs, ul = kMs, user_ul = kMs, user_dl = kMs, stop = kNoTick;
-  bool user_dl_set = false, dry_run = false, policy_set = false, quiet = false, show = false, node_stats = false;
+  bool user_dl_set = false, dry_run = false, policy_set = false, quiet = false, show = false, node_stats = false, user_stats = false;
   int policy = FOGNET_POLICY_REF_V3;
   double p_busy = -1.0, p_idle = -1.0;
 };
@@ -423,8 +423,9 @@ void hip_check(hipError_t e, const char* what) {
 // The publish traces of R replications (glibc seeds seed .. seed + R - 1).
 // Returns T (equal for every replication: the seed only changes MIPSRequired).
 // Replications r0 .. r0 + n - 1 of the job (glibc seed o.seed + r).
+// user_of (nullable): the publishing user of every trace entry, [n][T] (--user-stats).
 int32_t gen_traces(const Scenario& sc, const Options& o, int64_t user_dl, int r0, int n, std::vector<int64_t>& arrive,
-                   std::vector<int32_t>& req) {
+                   std::vector<int32_t>& req, std::vector<int32_t>* user_of = nullptr) {
   const int32_t U = (int32_t)sc.users.size();
   std::vector<int64_t> up(U, o.user_ul), dn(U, user_dl);
   // publishes per user <= (stop - start) / interval + 2 (the CONNACK publish)
@@ -437,22 +438,24 @@ int32_t gen_traces(const Scenario& sc, const Options& o, int64_t user_dl, int r0
   const int32_t cap = (int32_t)cap64;
   int32_t T = -1;
   std::vector<int64_t> a(cap);
-  std::vector<int32_t> q(cap);
+  std::vector<int32_t> q(cap), who(user_of ? cap : 0);
   for (int i = 0; i < n; ++i) {
     const int r = r0 + i;
     int32_t t = 0;
     check(fognet_gen_trace_mqtt(o.seed + (uint32_t)r, U, sc.u_start.data(), sc.u_interval.data(), up.data(), dn.data(),
-                                sc.stop, 200, 701, cap, a.data(), q.data(), nullptr, &t),
+                                sc.stop, 200, 701, cap, a.data(), q.data(), user_of ? who.data() : nullptr, &t),
           "fognet_gen_trace_mqtt");
     if (T < 0) {
       T = t;
       arrive.assign((size_t)n * T, 0);
       req.assign((size_t)n * T, 0);
+      if (user_of) user_of->assign((size_t)n * T, 0);
     } else if (t != T) {
       die("replications produced different publish counts");
     }
     std::copy(a.begin(), a.begin() + T, arrive.begin() + (size_t)i * T);
     std::copy(q.begin(), q.begin() + T, req.begin() + (size_t)i * T);
+    if (user_of) std::copy(who.begin(), who.begin() + T, user_of->begin() + (size_t)i * T);
   }
   return T;
 }
@@ -473,6 +476,8 @@ void usage() {
       "  --ring N             per-node pending capacity (power of two)\n"
       "  --trace-out FILE     write the FOGNTRC1 trace  --sca FILE / --vec FILE (replication 0)\n"
       "  --node-stats         with --sca: append one block per fog node (tasks, queueTime, response)\n"
+      "  --user-stats         with --sca (BrokerBaseApp3 runs from an ini): append one block per user module\n"
+      "                       (latency, latencyH1, taskTime) and the broker's delay\n"
       "  --device D           HIP device (default 0)\n"
       "  --world W --rank K --comm-id FILE   one process per GPU: rank K replays its block of the\n"
       "                       --reps replications; the job statistics are exchanged over RCCL\n"
@@ -527,6 +532,7 @@ Options parse_args(int argc, char** argv) {
     else if (a == "--quiet") o.quiet = true;
     else if (a == "--show") o.show = true;
     else if (a == "--node-stats") o.node_stats = true;
+    else if (a == "--user-stats") o.user_stats = true;
     else if (a == "--world") o.world = (int)parse_int(need(i), "--world");
     else if (a == "--rank") o.rank = (int)parse_int(need(i), "--rank");
     else if (a == "--comm-id") o.comm_id = need(i);
@@ -539,6 +545,10 @@ Options parse_args(int argc, char** argv) {
   if (o.reps <= 0) die("--reps must be > 0");
   if (o.world < 1 || o.rank < 0 || o.rank >= o.world) die("--world / --rank: need 0 <= rank < world");
   if (o.node_stats && o.world > 1) die("--node-stats: the per-node records of several ranks are not combined (--world 1)");
+  if (o.user_stats && o.sca.empty()) die("--user-stats appends to the job's .sca: give --sca FILE");
+  if (o.user_stats && o.world > 1) die("--user-stats: the per-user records of several ranks are not combined (--world 1)");
+  if (o.user_stats && !o.trace_in.empty()) die("--user-stats needs the ini's user modules (-f INI): a trace file names no users");
+  if (o.user_stats && o.user_dl < 0) die("--user-stats needs a broker->user latency (--user-dl none gives the acks no way back)");
   if (o.world > 1 && o.comm_id.empty()) die("--world > 1 needs --comm-id FILE (the communicator id's rendezvous)");
   if (o.reps < o.world) die("--reps must be >= --world (every rank replays a block of replications)");
   if (o.ring != 0 && (o.ring < 2 || o.ring > (1 << 15) || (o.ring & (o.ring - 1)) != 0))
@@ -672,7 +682,59 @@ void append_node_stats(const Options& o, fognet_ctx* ctx, const fognet_batch_in&
   check(fognet_write_sca_nodes(o.sca.c_str(), run_id.c_str(), network.c_str(), in.N, nodes.data(), nullptr, 1), "sca nodes");
 }
 
-int run_v3(const Options& o, fognet_batch_in in, const std::string& network, const std::string& run_id) {
+// what --user-stats adds to a BrokerBaseApp3 run: the users in --users order and every publish's user
+struct UserSide {
+  std::vector<std::string> modules;  // [U] module names as the ini spells them (user[3], usr[0], ...)
+  std::vector<int32_t> user_of;      // [R][T]
+};
+
+// --user-stats: the per-user records of the finished replay (fognet_per_user_stats_dev over device copies
+// of the trace, the per-task outputs and user_of, with the links --user-ul / --user-dl shared by all users),
+// reduced over the replications (fognet_reduce_user_stats_dev) and appended to the job's .sca, one block per
+// user module plus the broker's delay.
+void append_user_stats(const Options& o, fognet_ctx* ctx, const fognet_batch_in& in, const fognet_batch_out& out,
+                       const UserSide& us, const std::string& network, const std::string& run_id) {
+  const size_t R = (size_t)in.R, RT = R * (size_t)in.T, N = (size_t)in.N, NRN = (in.node_stride ? R : 1) * N;
+  const int32_t U = (int32_t)us.modules.size();
+  auto up = [](const auto* h, size_t n) {
+    return dev_copy(std::vector<std::remove_cv_t<std::remove_pointer_t<decltype(h)>>>(h, h + n));
+  };
+  fognet_batch_in din = in;
+  din.arrive_tick = up(in.arrive_tick, RT), din.req_mips = up(in.req_mips, RT), din.mips = up(in.mips, NRN);
+  din.dl_tick = up(in.dl_tick, NRN), din.ul_tick = up(in.ul_tick, NRN), din.init_adv_tick = up(in.init_adv_tick, NRN);
+  din.p_busy_w = din.p_idle_w = nullptr;
+  din.down_tick = nullptr;
+  fognet_batch_out dout{up(out.node, RT), up(out.status, RT), nullptr, up(out.done_tick, RT), up(out.stats, R),
+                        nullptr, nullptr};
+  int32_t* d_user_of = dev_copy(us.user_of);
+  int64_t* d_ul = dev_copy(std::vector<int64_t>(U, o.user_ul));
+  int64_t* d_dl = dev_copy(std::vector<int64_t>(U, o.user_dl));
+  fognet_user_stats* d_users = dev_alloc<fognet_user_stats>(R * (size_t)U);
+  fognet_user_stats* d_job = dev_alloc<fognet_user_stats>(U);
+  int64_t* d_un = dev_alloc<int64_t>(R);
+  check_ctx(ctx, fognet_per_user_stats_dev(ctx, &din, &dout, d_user_of, U, 0, d_ul, d_dl, d_users, d_un, nullptr),
+            "fognet_per_user_stats_dev");
+  check_ctx(ctx, fognet_reduce_user_stats_dev(ctx, d_users, dout.stats, in.R, U, d_job, nullptr),
+            "fognet_reduce_user_stats_dev");
+  std::vector<fognet_user_stats> users(U);
+  std::vector<int64_t> un(R);
+  hip_check(hipMemcpy(users.data(), d_job, (size_t)U * sizeof(fognet_user_stats), hipMemcpyDeviceToHost), "hipMemcpy");
+  hip_check(hipMemcpy(un.data(), d_un, R * sizeof(int64_t), hipMemcpyDeviceToHost), "hipMemcpy");
+  const void* bufs[] = {din.arrive_tick, din.req_mips, din.mips, din.dl_tick, din.ul_tick, din.init_adv_tick, dout.node,
+                        dout.status, dout.done_tick, dout.stats, d_user_of, d_ul, d_dl, d_users, d_job, d_un};
+  for (const void* b : bufs) (void)hipFree(const_cast<void*>(b));
+  for (size_t r = 0; r < R; ++r)
+    if (un[r] != 0)
+      die("--user-stats: replication " + std::to_string(r) + " has " + std::to_string(un[r]) +
+          " publishes of no known user");
+  std::vector<const char*> names(U);
+  for (int32_t u = 0; u < U; ++u) names[u] = us.modules[u].c_str();
+  check(fognet_write_sca_users(o.sca.c_str(), run_id.c_str(), network.c_str(), U, users.data(), names.data(), 1),
+        "sca users");
+}
+
+int run_v3(const Options& o, fognet_batch_in in, const std::string& network, const std::string& run_id,
+           const UserSide* us = nullptr) {
   const size_t RT = (size_t)in.R * (size_t)in.T;
   std::vector<int32_t> node(RT);
   std::vector<uint8_t> status(RT);
@@ -713,6 +775,7 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
   }
   if (!o.sca.empty()) check(fognet_write_sca(o.sca.c_str(), run_id.c_str(), network.c_str(), &job, hist.data()), "sca");
   if (!o.sca.empty() && o.node_stats) append_node_stats(o, ctx, in, out, network, run_id);
+  if (!o.sca.empty() && o.user_stats && us) append_user_stats(o, ctx, in, out, *us, network, run_id);
   if (!o.vec.empty()) {  // replication 0's vectors (a failed replication has no complete outputs)
     if (stats[0].status != FOGNET_OK)
       die(std::string("--vec: replication 0 failed: ") + fognet_status_string(stats[0].status));
@@ -867,6 +930,8 @@ int main(int argc, char** argv) {
   if (!v2 && sc.broker_type != "BrokerBaseApp3" && sc.broker_type != "BrokerBaseAppHip")
     die("broker module " + sc.broker_type + " is not on the engine's path (BrokerBaseApp3, BrokerBaseApp2)");
   if (v2 && o.policy_set) die("--policy applies to BrokerBaseApp3 runs");
+  if (v2 && o.user_stats)
+    die("--user-stats applies to BrokerBaseApp3 runs (the BrokerBaseApp2 model has no closed form for the user signals)");
   const int32_t N = (int32_t)sc.mips.size();
   // BrokerBaseApp2 does not answer a user's CONNECT with a CONNACK, so its
   // users publish from startTime + sendInterval on
@@ -876,7 +941,9 @@ int main(int argc, char** argv) {
   // rank's contiguous block of the job's replications (the first reps % world ranks take one more)
   const int q = o.reps / o.world, rem = o.reps % o.world;
   const int r0 = o.rank * q + std::min(o.rank, rem), nr = q + (o.rank < rem ? 1 : 0);
-  const int32_t T = gen_traces(sc, o, user_dl, r0, nr, arrive, req);
+  UserSide us;
+  us.modules = sc.users;
+  const int32_t T = gen_traces(sc, o, user_dl, r0, nr, arrive, req, o.user_stats ? &us.user_of : nullptr);
 
   // node k: CONNECT at startTime reaches the broker after ul, the CONNACK
   // comes back after dl, the first ADVERTISEMIPS fires 0.01 s later
@@ -942,5 +1009,5 @@ int main(int argc, char** argv) {
     if (o.world > 1) die("BrokerBaseApp2 replays run on one GPU (--world 1)");
     return run_v2(o, sc, T, arrive, req, dl, ul, first_adv, run_id);
   }
-  return run_v3(o, in, sc.network, run_id);
+  return run_v3(o, in, sc.network, run_id, o.user_stats ? &us : nullptr);
 }

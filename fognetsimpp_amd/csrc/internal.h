@@ -430,6 +430,15 @@ int32_t node_stats_lds_max();
 hipError_t launch_node_stats(const ReplayArgs& a, fognet_node_stats* out, bool force_hbm, hipStream_t s);
 hipError_t launch_reduce_node_stats(const fognet_node_stats* in, const fognet_rep_stats* stats, int32_t R, int32_t N,
                                     fognet_node_stats* out, hipStream_t s);
+// Per-user signals of a finished replay and their job reduction (per_user_stats.hip).  Up to
+// per_user_stats_lds_max() users the accumulators and the user links live in LDS unless force_hbm;
+// the reduction is one workgroup per user over any R and needs no workspace.
+int32_t per_user_stats_lds_max();
+hipError_t launch_per_user_stats(const ReplayArgs& a, const int32_t* user_of, int32_t U, int32_t link_stride,
+                                 const int64_t* user_ul, const int64_t* user_dl, fognet_user_stats* out,
+                                 int64_t* n_unassigned, bool force_hbm, hipStream_t s);
+hipError_t launch_reduce_user_stats(const fognet_user_stats* in, const fognet_rep_stats* stats, int32_t R, int32_t U,
+                                    fognet_user_stats* out, hipStream_t s);
 // v2 model replay (replay_v2.hip)
 size_t replay_v2_workspace_bytes(int32_t R, int32_t T, int32_t N, int32_t q_log2);
 hipError_t launch_replay_v2(const fognet_v2_in& in, const fognet_v2_out& out, void* workspace, int32_t q_log2,

@@ -502,6 +502,57 @@ int fognet_write_sca_nodes(const char* path, const char* run_id, const char* net
   return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_sca_nodes: write failed: ") + path);
 }
 
+// one fognet_moments of raw emitted values as a .sca statistic (recorded value raw * 1e-12)
+static void moments_statistic(FILE* f, const std::string& mod, const char* name, const fognet_moments& m) {
+  // the 128-bit two's complement sum, sign-extended to the 192 bits moments() takes
+  const uint64_t S[3] = {m.sum_lo, m.sum_hi, (int64_t)m.sum_hi < 0 ? ~(uint64_t)0 : 0};
+  const uint64_t Q[3] = {m.sq_lo, m.sq_hi, m.sq_top};
+  statistic(f, mod, name, "stats", moments(m.count, S, Q, m.min_raw, m.max_raw, true, true));
+  stat_attrs(f, name, "stats");
+  if (m.overflow > 0)
+    fprintf(f, "scalar %s \t\"%s emissions lost\" \t%lld\n", mod.c_str(), name, (long long)m.overflow);
+}
+
+int fognet_write_sca_users(const char* path, const char* run_id, const char* network, int32_t U,
+                           const fognet_user_stats* users, const char* const* user_module, int append) {
+  if (!path || !run_id || !network || U < 0 || (U > 0 && !users))
+    return fail(FOGNET_ERR_ARG, "write_sca_users: bad argument");
+  if (user_module)
+    for (int32_t u = 0; u < U; ++u)
+      if (!user_module[u]) return fail(FOGNET_ERR_ARG, "write_sca_users: null module name");
+  FILE* f = fopen(path, append ? "a" : "w");
+  if (!f) return fail(FOGNET_ERR_ARG, std::string("write_sca_users: cannot open ") + path);
+  if (!append) run_header(f, run_id, network);
+  fognet_moments delay = {};  // the broker's signal: the exact merge of the users' shares
+  delay.min_raw = INT64_MAX;
+  delay.max_raw = INT64_MIN;
+  for (int32_t u = 0; u < U; ++u) {
+    const fognet_user_stats& s = users[u];
+    const std::string mod = std::string(network) + "." +
+                            (user_module ? std::string(user_module[u]) : "user[" + std::to_string(u) + "]") + ".udpApp[0]";
+    moments_statistic(f, mod, "latency", s.latency);
+    moments_statistic(f, mod, "latencyH1", s.latencyH1);
+    moments_statistic(f, mod, "taskTime", s.taskTime);
+    const fognet_moments& d = s.delay;
+    delay.count += d.count;
+    delay.overflow += d.overflow;
+    if (d.min_raw < delay.min_raw) delay.min_raw = d.min_raw;
+    if (d.max_raw > delay.max_raw) delay.max_raw = d.max_raw;
+    unsigned __int128 c = (unsigned __int128)delay.sum_lo + d.sum_lo;  // modulo 2^128 / 2^192
+    delay.sum_lo = (uint64_t)c;
+    delay.sum_hi = delay.sum_hi + d.sum_hi + (uint64_t)(c >> 64);
+    c = (unsigned __int128)delay.sq_lo + d.sq_lo;
+    delay.sq_lo = (uint64_t)c;
+    c = (unsigned __int128)delay.sq_hi + d.sq_hi + (uint64_t)(c >> 64);
+    delay.sq_hi = (uint64_t)c;
+    delay.sq_top = delay.sq_top + d.sq_top + (uint64_t)(c >> 64);
+  }
+  // delay is the broker module's signal (BrokerBaseApp3.cc:143), a simtime_t in s
+  moments_statistic(f, std::string(network) + ".broker.udpApp[0]", "delay", delay);
+  const bool ok = ferror(f) == 0;
+  return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_sca_users: write failed: ") + path);
+}
+
 int fognet_write_vec(const char* path, const char* run_id, const char* network, int32_t T, int32_t N,
                      const int64_t* arrive_tick, const int64_t* dl_tick, const int32_t* node, const uint8_t* status,
                      const int64_t* start_tick, const int32_t* node_id) {

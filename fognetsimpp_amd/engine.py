@@ -505,6 +505,103 @@ def merge_node_stats(records) -> np.ndarray:
     return np.frombuffer(bytes(acc), dtype=_abi.NODE_STATS_DTYPE).copy()
 
 
+def per_user_stats(ctx: Context, trace: dict, out: BatchResult, user_of, user_ul, user_dl,
+                   policy: str | int | None = None, res: torch.Tensor | None = None,
+                   hier_up_tick: int | None = None, allow_unassigned: bool = False,
+                   n_unassigned: torch.Tensor | None = None):
+    """Per-user signals (fognet_per_user_stats_dev) of a finished replay on the current
+    stream: what the reference records per user module.  ``user_of``: the publishing
+    user of every trace entry, int32 [R, T]; ``user_ul`` / ``user_dl``: the users' links,
+    [U] (shared by all replications) or [R, U]; host arrays or device tensors.  Returns
+    ``(records, n_unassigned)``: the device buffer uint8 [R, U * sizeof(fognet_user_stats)]
+    (``.cpu().numpy().view(_abi.USER_STATS_DTYPE)`` gives [R, U] records) and the int64 [R]
+    device tensor of decided publishes whose user lies outside [0, U).  A non-zero count
+    raises FognetError (FOGNET_ERR_ARG) unless ``allow_unassigned`` (this check
+    synchronises).  ``res`` / ``n_unassigned``: write the records / the counts (int64 [R])
+    into these buffers instead of new ones.
+    ``policy`` and ``hier_up_tick``: as for :func:`user_stats` (None: what run_batch
+    recorded on ``out``); EXT_HIER needs ``out.escalated`` and is refused without it."""
+    arrive = trace["arrive"]
+    R, T = arrive.shape
+    dev = arrive.device
+
+    def on_dev(x, dt):
+        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        return t.to(device=dev, dtype=dt).contiguous()
+    uo, uu, ud = on_dev(user_of, torch.int32), on_dev(user_ul, torch.int64), on_dev(user_dl, torch.int64)
+    if tuple(uo.shape) != (R, T):
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"user_of must have shape [R, T], got {tuple(uo.shape)}")
+    U = uu.shape[-1] if uu.dim() else -1
+    if uu.shape != ud.shape or tuple(uu.shape) not in ((U,), (R, U)):
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"user links must both have shape [U] or [R, U], got "
+                                               f"{tuple(uu.shape)} / {tuple(ud.shape)}")
+    mips = trace["mips"]
+    N = mips.shape[-1]
+    nres = R * U * _abi.USER_STATS_DTYPE.itemsize
+    if res is None:
+        res = torch.empty(nres, dtype=torch.uint8, device=dev)
+    else:
+        _check_bytes(res, nres, dev, "res")
+    un = n_unassigned if n_unassigned is not None else torch.empty(R, dtype=torch.int64, device=dev)
+    if un.dtype != torch.int64 or un.numel() != R or un.device != dev or not un.is_contiguous():
+        raise FognetError(_abi.FOGNET_ERR_ARG, "n_unassigned must be a contiguous int64 [R] tensor on the trace's device")
+    if policy is None:
+        policy = out.policy if out.policy is not None else _abi.FOGNET_POLICY_REF_V3
+    pol = POLICIES[policy] if isinstance(policy, str) else int(policy)
+    hier = pol == _abi.FOGNET_POLICY_EXT_HIER
+    bi = _abi.BatchIn(R, T, N, pol, N if mips.dim() == 2 else 0, 0,
+                      _ptr(arrive), _ptr(trace["req"]), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
+                      _ptr(trace["init"]), None, None, None, _ptr(trace.get("region")) if hier else None,
+                      _hier_up(out, hier_up_tick) if hier else 0)
+    bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick),
+                       _ptr(out.stats), None, None, _ptr(out.escalated) if hier else None)
+    ctx.check(ctx._lib.fognet_per_user_stats_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(uo), U,
+                                                 U if uu.dim() == 2 else 0, _ptr(uu), _ptr(ud), _ptr(res), _ptr(un),
+                                                 _stream_ptr(dev)), "per_user_stats")
+    if not allow_unassigned and R > 0:
+        bad = int(un.sum().item())
+        if bad:
+            raise FognetError(_abi.FOGNET_ERR_ARG, f"per_user_stats: {bad} decided publishes name a user outside "
+                                                   f"[0, {U}) (allow_unassigned=True leaves them out)")
+    return res[:nres].view(R, U * _abi.USER_STATS_DTYPE.itemsize), un
+
+
+def reduce_user_stats(ctx: Context, user_stats: torch.Tensor, stats: torch.Tensor, R: int, U: int,
+                      out: torch.Tensor | None = None) -> np.ndarray:
+    """Exact job reduction of user records on the device (fognet_reduce_user_stats_dev):
+    record u merges user u over the replications whose status is OK.  ``user_stats``:
+    :func:`per_user_stats`'s buffer, or with U = 1 the [R] records of :func:`user_stats`
+    as a device buffer; ``stats``: the replications' records (BatchResult.stats).
+    Returns USER_STATS_DTYPE [U]; ``out``: the device buffer written to (uint8,
+    U * sizeof(fognet_user_stats))."""
+    nout = U * _abi.USER_STATS_DTYPE.itemsize
+    dev = stats.device
+    if out is None:
+        out = torch.empty(max(nout, 1), dtype=torch.uint8, device=dev)
+    else:
+        _check_bytes(out, nout, dev, "out")
+    if user_stats.numel() < R * nout or stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "user_stats / stats smaller than R replications")
+    ctx.check(ctx._lib.fognet_reduce_user_stats_dev(ctx.handle, _ptr(user_stats), _ptr(stats), R, U, _ptr(out),
+                                                    _stream_ptr(dev)), "reduce_user_stats")
+    return out[:nout].cpu().numpy().view(_abi.USER_STATS_DTYPE)
+
+
+def merge_user_stats(records) -> np.ndarray:
+    """Exact host merge of user record arrays [U] (e.g. one per GPU after an
+    all-gather; fognet_user_stats_merge) into one [U]."""
+    lib = _abi.load()
+    records = [np.ascontiguousarray(r, dtype=_abi.USER_STATS_DTYPE).reshape(-1) for r in records]
+    U = records[0].size if records else 0
+    acc = (_abi.UserStats * U)()
+    for u in range(U):
+        lib.fognet_user_stats_init(C.byref(acc[u]))
+        for rec in records:
+            b = _abi.UserStats.from_buffer_copy(rec[u].tobytes())
+            lib.fognet_user_stats_merge(C.byref(acc[u]), C.byref(b))
+    return np.frombuffer(bytes(acc), dtype=_abi.USER_STATS_DTYPE).copy()
+
+
 @dataclass
 class V2Result:
     node: torch.Tensor        # [R, T] int32 (-1: served by the broker / no node)

@@ -111,6 +111,24 @@ def write_sca_nodes(path: str, nodes, node_id=None, append: bool = False, run_id
                                               _p(nid), 1 if append else 0), "write_sca_nodes")
 
 
+def write_sca_users(path: str, users, user_module=None, append: bool = False, run_id: str = "General-0-fognet",
+                    network: str = "FogNet") -> None:
+    """Per-user `.sca` blocks of USER_STATS_DTYPE records [U] (fognet_write_sca_users):
+    `latency`, `latencyH1` and `taskTime` under <network>.<user_module[u] or "user[u]">.udpApp[0]
+    each, then the broker's `delay` from the merge of the records.  ``append``: add them to
+    the file :func:`write_sca` wrote instead of starting a new one."""
+    rec = np.ascontiguousarray(users, dtype=_abi.USER_STATS_DTYPE).reshape(-1)
+    names = None
+    if user_module is not None:
+        mods = [str(m).encode() for m in user_module]
+        if len(mods) != rec.size:
+            raise FognetError(_abi.FOGNET_ERR_ARG, "write_sca_users: user_module length differs from the records'")
+        names = (C.c_char_p * len(mods))(*mods)
+    _check(_abi.load().fognet_write_sca_users(path.encode(), run_id.encode(), network.encode(), rec.size, _p(rec),
+                                              C.cast(names, C.c_void_p) if names is not None else None,
+                                              1 if append else 0), "write_sca_users")
+
+
 def write_vec(path: str, arrive, dl, node, status, start, node_id=None, run_id: str = "General-0-fognet",
               network: str = "FogNet") -> None:
     """OMNeT++ .vec of ONE replication: arrive/node/status/start [T], dl [N]."""

@@ -321,6 +321,10 @@ typedef struct fognet_batch_out {
  *   The per-node records (fognet_node_stats_dev's [R][N], fognet_reduce_node_stats_dev's [N])
  *     obey every sentence above: 8-B alignment, nothing outside [R][N] / [N] touched, no
  *     initialisation needed; a failed replication's row is N empty records.
+ *   The per-user records (fognet_per_user_stats_dev's [R][U], fognet_reduce_user_stats_dev's
+ *     [U]) and n_unassigned [R] likewise: 8-B alignment (user_of: 4 B), nothing outside
+ *     [R][U] / [U] / [R] touched, no initialisation needed; a failed replication's row is U
+ *     empty records and its n_unassigned is 0.
  *   escalated likewise: 1-B alignment, nothing outside [R][T] touched, no initialisation
  *     needed; a failed replication's row is undefined, like its other per-task rows. */
 
@@ -563,6 +567,53 @@ int fognet_reduce_node_stats_dev(fognet_ctx *ctx, const fognet_node_stats *node_
 /* Host-side identity and exact merge (ranks combine their [N] records after an all-gather). */
 void fognet_node_stats_init(fognet_node_stats *s);
 void fognet_node_stats_merge(fognet_node_stats *acc, const fognet_node_stats *other);
+
+/* Per-user signals of a finished replay (fognet_run_batch_dev or fognet_replay_dev on the
+ * same stream): device pointers in `in` (arrive_tick, dl_tick, ul_tick) and `out` (node,
+ * status, done_tick, stats[r].{n_tasks,status}), the publishing user of every trace entry
+ * user_of [R][T] (device; fognet_gen_trace_mqtt's user_of) and the users' links
+ * user_ul_tick / user_dl_tick [U] shared by all replications (link_stride = 0) or [R][U]
+ * (link_stride = U).  Writes per_user [R][U] (device): record [r][u] covers the publishes
+ * i < stats[r].n_tasks of replication r with user_of[r][i] == u.  The four signals and
+ * their emission rule are fognet_user_stats_dev's, task i's links being
+ * user_ul_tick[user_of[i]] and user_dl_tick[user_of[i]]: delay for every publish, the
+ * broker's own pubAck into latencyH1 for every publish, the node ack at arrive_tick + dl_k
+ * + in->hier_up_tick * escalated[i] into latency (status 5) or latencyH1 (status 4),
+ * taskTime where done_tick >= 0; an emission whose product leaves the simtime_t range
+ * counts in overflow.  A user without a publish gets the count == 0 record.
+ * Defining invariant: the exact merge (fognet_user_stats_merge) of a replication's U records
+ * equals, bit for bit, fognet_user_stats_dev's record of that replication with
+ * user_per_task = 1 and the per-task links expanded from user_of.
+ * FOGNET_POLICY_REF_V3 and FOGNET_POLICY_EXT_LAT, with or without down_tick;
+ * FOGNET_POLICY_EXT_HIER with out->escalated (the replay's flags).  Refused:
+ * FOGNET_POLICY_EXT_HIER with out->escalated NULL (FOGNET_ERR_UNSUPPORTED, before anything
+ * else is checked and with nothing written); a statistics-only `out`, a NULL per_user or
+ * NULL links with R * U > 0, a NULL user_of with R * T > 0, U < 0 and a link_stride other
+ * than 0 or U (FOGNET_ERR_ARG).  Under the other policies escalated is not read.
+ * A failed replication (status other than FOGNET_OK / FOGNET_REF_ABORTED) gets U count == 0
+ * records and n_unassigned[r] = 0; nothing of its per-task rows, its user_of row or its link
+ * row is read (a FOGNET_REF_ABORTED one keeps its full records).
+ * A decided publish whose user_of lies outside [0, U) adds to no record and touches nothing
+ * out of bounds; n_unassigned [R] (device, nullable) receives their number per replication.
+ * U = 0 writes nothing but n_unassigned.
+ * FOGNET_USER_STATS=hbm (environment, testing): the accumulators are the caller's records
+ * for every U, as they are above 128 users; the results are identical. */
+int fognet_per_user_stats_dev(fognet_ctx *ctx, const fognet_batch_in *in, const fognet_batch_out *out,
+                              const int32_t *user_of, int32_t U, int32_t link_stride,
+                              const int64_t *user_ul_tick, const int64_t *user_dl_tick,
+                              fognet_user_stats *per_user, int64_t *n_unassigned, void *hip_stream);
+/* Job reduction of user records (device pointers): out[u] = the exact merge of
+ * user_stats[r][u] over the replications with stats[r].status == FOGNET_OK
+ * (fognet_reduce_node_stats_dev's rule: REF_ABORTED and failed ones contribute nothing).
+ * Any R; R = 0 gives U empty records.  Needs no workspace.  With U = 1 it reduces the [R]
+ * records of fognet_user_stats_dev. */
+int fognet_reduce_user_stats_dev(fognet_ctx *ctx, const fognet_user_stats *user_stats,
+                                 const fognet_rep_stats *stats, int32_t R, int32_t U,
+                                 fognet_user_stats *out, void *hip_stream);
+/* Host-side identity (the count == 0 record in all four signals) and exact merge, field by
+ * field (ranks combine their [U] records after an all-gather). */
+void fognet_user_stats_init(fognet_user_stats *s);
+void fognet_user_stats_merge(fognet_user_stats *acc, const fognet_user_stats *other);
 
 /* Exact reduction of R per-replication stats (device pointers) into one job
  * record (device pointer).  Replications with status != OK count in n_failed

@@ -99,6 +99,20 @@ int fognet_write_sca(const char *path, const char *run_id, const char *network, 
 int fognet_write_sca_nodes(const char *path, const char *run_id, const char *network, int32_t N,
                            const fognet_node_stats *nodes, const int32_t *node_id, int append);
 
+/* OMNeT++ .sca blocks of per-user records (host; fognet_per_user_stats_dev /
+ * fognet_reduce_user_stats_dev, fognet_hip.h): per module
+ * <network>.<user_module[u] or "user[u]">.udpApp[0] the statistics `latency:stats`,
+ * `latencyH1:stats` and `taskTime:stats` in ms (raw * 1e-12) with fognet_write_sca's
+ * fields and formatting, computed from the exact sums (a user without an emission
+ * writes them with count 0), each followed by a scalar "<signal> emissions lost" where
+ * its overflow > 0.  Then one `delay:stats` (s) under <network>.broker.udpApp[0] from the
+ * exact merge of the U records' delay: it is the broker module's signal
+ * (BrokerBaseApp3.cc:143), not a user module's.  append != 0: the blocks are appended to
+ * the existing file fognet_write_sca wrote, without a second version/run header;
+ * otherwise the file is created with one.  user_module: [U] names, nullable. */
+int fognet_write_sca_users(const char *path, const char *run_id, const char *network, int32_t U,
+                           const fognet_user_stats *users, const char *const *user_module, int append);
+
 /* OMNeT++ .vec of one replication's per-task outputs (host arrays of length
  * T): vector `queueTime:vector` of every fog node module
  * <network>.fogNode[<node_id or index>].udpApp[0] (value ms, emitted at the
