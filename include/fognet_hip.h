@@ -25,6 +25,26 @@
  *   - The caller owns every buffer.  *_dev entry points take device pointers
  *     (hipMalloc'd, or torch.cuda tensors) and enqueue on the given hipStream_t
  *     (NULL = default stream); the others take host pointers and copy.
+ *   - Streams.  A *_dev call only enqueues: every kernel, clear and copy it
+ *     issues goes to hip_stream and to no other stream, and the call returns
+ *     without waiting for the device.  The one exception is a call that has to
+ *     grow the context's workspace (the first job of a size larger than any
+ *     before it on that context): it frees the old allocation, which waits
+ *     for the device.  The calls on one context share that workspace, so
+ *     consecutive *_dev calls on one context must be ordered with respect to
+ *     each other: enqueue them on one stream, or order the streams with
+ *     events (a statistics or reduction pass after its replay likewise).
+ *     Contexts share nothing; two contexts may run on two streams at once.
+ *     The host-pointer entry points (fognet_decide, fognet_decide_window,
+ *     fognet_decide_v2, fognet_run_batch) run on a private non-blocking
+ *     stream of the context and return once their results are in the caller's
+ *     memory.  The decisions wait for that stream alone, not for the
+ *     caller's streams; fognet_run_batch frees its staging buffers before
+ *     it returns, which waits for the whole device.  fognet_run_batch
+ *     uses the workspace as well: do not call it while a *_dev job of the
+ *     same context is executing.  (A job that is enqueued but still waits
+ *     behind other work of its stream is unaffected: every job initialises
+ *     what it reads of the workspace when it starts.)
  *   - A fognet_ctx is not thread-safe; use one per host thread (OMNeT++'s
  *     sequential kernel is single-threaded anyway).
  *   - Deterministic: identical inputs give bit-identical outputs.
@@ -618,8 +638,8 @@ void fognet_user_stats_merge(fognet_user_stats *acc, const fognet_user_stats *ot
 /* Exact reduction of R per-replication stats (device pointers) into one job
  * record (device pointer).  Replications with status != OK count in n_failed
  * and contribute nothing else.  R > 4096 reduces through partial records in
- * the context's workspace: reductions on one context must then be enqueued
- * on one stream (or synchronised), since concurrent ones share it. */
+ * the context's workspace (ordering of calls on one context: "Streams" in
+ * the Conventions above). */
 int fognet_reduce_stats_dev(fognet_ctx *ctx, const fognet_rep_stats *stats, int32_t R,
                             fognet_job_stats *out, void *hip_stream);
 /* Host-side exact merge (used to combine per-GPU records after an all-gather):

@@ -29,6 +29,8 @@ The shapes are the smallest that still cross each edge (T = 1, 63, 65, 129,
 for the reduction's block edge)."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -117,18 +119,25 @@ CASES = [
 _cache: dict = {}
 
 
-def batch_inputs(c):
-    """Host trace, run_batch keywords and the oracle's result of a batch case (computed once)."""
-    if c["id"] in _cache:
-        return _cache[c["id"]]
+def _key(c, decoy):
+    return c["id"] + ("/decoy" if decoy else "")
+
+
+def batch_inputs(c, decoy=False):
+    """Host trace, run_batch keywords and the oracle's result of a batch case (computed once).
+    ``decoy``: a valid trace of the same shapes and kind from other seeds, without the oracle's
+    result (None): what tests/stream_gate.py leaves in the input views until the gate opens."""
+    if _key(c, decoy) in _cache:
+        return _cache[_key(c, decoy)]
     R, N, T = c["R"], c["N"], c["T"]
     sp = c.get("special")
+    ds = 100 if decoy else 0
     if sp == "handover":  # an overloaded replication among light ones, as test_ring_capacity_exceeded (at
         # rho = 0.01 the light ones keep at most 3 tasks pending: they stay on the register kernel)
-        over, light = tg.make_batch(11, 1, N, T, rho=3.0), tg.make_batch(12, 2, N, T, rho=0.01)
+        over, light = tg.make_batch(11 + ds, 1, N, T, rho=3.0), tg.make_batch(12 + ds, 2, N, T, rho=0.01)
         tr = {k: np.concatenate([light[k][:1], over[k], light[k][1:]]) for k in over}
     else:
-        tr = tg.make_batch(c["seed"], R, N, T, rho=c["rho"])
+        tr = tg.make_batch(c["seed"] + ds, R, N, T, rho=c["rho"])
     tr = {k: v.copy() for k, v in tr.items()}
     if c.get("power", True):
         tr["p_busy"], tr["p_idle"] = fa.power_model(tr["mips"])
@@ -138,100 +147,139 @@ def batch_inputs(c):
     elif c.get("failed"):
         tr["mips"][1, 0] = 0
     if sp == "down":
-        tr = with_crashes(tr, seed=N)
+        tr = with_crashes(tr, seed=N + ds)
     kw = dict(policy=c.get("policy", "REF_V3"), ring_capacity=c.get("ring", 0))
     okw = {}
     if sp == "hier":
         tr["region"] = fa.mobility_regions(tr["arrive"], N)
         kw.update(HIER_KW)
         okw = dict(region=tr["region"], **HIER_KW)
-    o = ol.run_batch(tr["arrive"], tr["req"], tr["mips"], tr["dl"], tr["ul"], tr["init"], threads=R, hist=True,
-                     policy=ol.POLICIES[kw["policy"]], p_busy=tr.get("p_busy"), p_idle=tr.get("p_idle"),
-                     down=tr.get("down"), **okw)
-    _cache[c["id"]] = (tr, kw, o)
-    return _cache[c["id"]]
+    o = None if decoy else ol.run_batch(
+        tr["arrive"], tr["req"], tr["mips"], tr["dl"], tr["ul"], tr["init"], threads=R, hist=True,
+        policy=ol.POLICIES[kw["policy"]], p_busy=tr.get("p_busy"), p_idle=tr.get("p_idle"), down=tr.get("down"), **okw)
+    _cache[_key(c, decoy)] = (tr, kw, o)
+    return _cache[_key(c, decoy)]
 
 
-def generated_inputs(c):
-    if c["id"] not in _cache:
+def generated_inputs(c, decoy=False):
+    """``decoy``: the parameters of the next replications (every row another load and latency
+    scale) and another power model; the seed and r0, which are arguments, stay."""
+    if _key(c, decoy) not in _cache:
         R, N, T, seed, r0 = c["R"], c["N"], c["T"], 0x5EED0004, 11
-        mg, sc = fa.sweep_params(np.arange(r0, r0 + R), N)
+        mg, sc = fa.sweep_params(np.arange(r0, r0 + R) + (1 if decoy else 0), N)
         reps = [tg.make_replication(seed, r0 + r, N, T, lat_scale=int(sc[r]), mean_gap_ticks=float(mg[r]))
                 for r in range(R)]
         tr = {k: np.stack([rp[k] for rp in reps]) for k in reps[0]}
         pb = pi = None
         if c["power"]:
-            pb, pi = fa.power_model(tr["mips"])
-        o = ol.run_batch(tr["arrive"], tr["req"], tr["mips"], tr["dl"], tr["ul"], tr["init"], threads=R, hist=True,
-                         p_busy=pb, p_idle=pi)
-        _cache[c["id"]] = (seed, r0, mg, sc, pb, pi, o)
-    return _cache[c["id"]]
+            pb, pi = fa.power_model(tr["mips"] * 2 if decoy else tr["mips"])
+        o = None if decoy else ol.run_batch(tr["arrive"], tr["req"], tr["mips"], tr["dl"], tr["ul"], tr["init"],
+                                            threads=R, hist=True, p_busy=pb, p_idle=pi)
+        _cache[_key(c, decoy)] = (seed, r0, mg, sc, pb, pi, o)
+    return _cache[_key(c, decoy)]
 
 
-def user_inputs(c):
-    if c["id"] not in _cache:
+def user_inputs(c, decoy=False):
+    if _key(c, decoy) not in _cache:
         R, N, T = 3, 64, c.get("T", 65)
-        tr = {k: v.copy() for k, v in tg.make_batch(0x5EED0003, R, N, T, rho=0.9).items()}
+        tr = {k: v.copy() for k, v in tg.make_batch(0x5EED0003 + (100 if decoy else 0), R, N, T, rho=0.9).items()}
         if c["failed"] == "mid":
             tr["arrive"][1, T // 2] = tr["arrive"][1, T // 2 - 1] - 1
         elif c["failed"]:
             tr["mips"][1, 0] = 0
-        rng = np.random.default_rng(31)
+        rng = np.random.default_rng(32 if decoy else 31)
         shape = (R, T) if c["per_task"] else (R,)
         uu = rng.integers(0, 5 * 10**9, shape).astype(np.int64)
         ud = rng.integers(0, 5 * 10**9, shape).astype(np.int64)
-        o = ol.run_batch(tr["arrive"], tr["req"], tr["mips"], tr["dl"], tr["ul"], tr["init"], threads=R, user_ul=uu,
-                         user_dl=ud)
-        _cache[c["id"]] = (tr, uu, ud, o)
-    return _cache[c["id"]]
+        o = None if decoy else ol.run_batch(tr["arrive"], tr["req"], tr["mips"], tr["dl"], tr["ul"], tr["init"],
+                                            threads=R, user_ul=uu, user_dl=ud)
+        _cache[_key(c, decoy)] = (tr, uu, ud, o)
+    return _cache[_key(c, decoy)]
 
 
-def v2_inputs(c):
-    if c["id"] not in _cache:
-        tr, broker, stop, rt = v2_random(900 + 7 * c["R"] + c["N"], c["R"], c["N"], c["T"])
-        o = ol.run_v2(tr["arrive"], tr["req"], broker, tr["mips"], tr["dl"], tr["ul"], tr["first_adv"], stop, rt,
-                      threads=c["R"])
-        assert (o["stats"]["status"] == 0).all()
+def v2_inputs(c, decoy=False):
+    if _key(c, decoy) not in _cache:
+        tr, broker, stop, rt = v2_random(900 + 7 * c["R"] + c["N"] + (5000 if decoy else 0), c["R"], c["N"], c["T"])
+        o = None
+        if not decoy:
+            o = ol.run_v2(tr["arrive"], tr["req"], broker, tr["mips"], tr["dl"], tr["ul"], tr["first_adv"], stop, rt,
+                          threads=c["R"])
+            assert (o["stats"]["status"] == 0).all()
         stop = stop.astype(np.int64)
         if c.get("failed"):
             stop[1] = 2**53 + 1  # (the oracle's rows 0 and 2 are the reference; row 1 is refused)
-        _cache[c["id"]] = (tr, broker.astype(np.int32), stop, rt.astype(np.float64), o)
-    return _cache[c["id"]]
+        _cache[_key(c, decoy)] = (tr, broker.astype(np.int32), stop, rt.astype(np.float64), o)
+    return _cache[_key(c, decoy)]
 
 
-def decide_inputs(c):
-    if c["id"] not in _cache:
+def decide_inputs(c, decoy=False):
+    if _key(c, decoy) not in _cache:
         m, n = c["m"], c["n"]
-        rng = np.random.default_rng(1000 * m + n)
+        rng = np.random.default_rng(1000 * m + n + (500000 if decoy else 0))
         if c["kind"] == "decide3":  # as test_decide_batch_matches_oracle
             busy = rng.integers(0, 6, size=(m, n)).astype(np.float64) + rng.choice([0.0, 0.5, 1e-16], size=(m, n))
             busy[rng.random((m, n)) < 0.01] = np.nan
             mips = rng.integers(1, 3000, size=(m, n)).astype(np.int32)
             mips[rng.random(m) < 0.05, 0] = 0
             req = rng.integers(-5000, 70000, size=m).astype(np.int32)
-            want = [ol.decide_v3(busy[q], mips[q], int(req[q])) for q in range(m)]
-            _cache[c["id"]] = (busy, mips, req, want)
+            want = None if decoy else [ol.decide_v3(busy[q], mips[q], int(req[q])) for q in range(m)]
+            _cache[_key(c, decoy)] = (busy, mips, req, want)
         else:  # as test_decide_v2_batch_matches_oracle
             mips = rng.choice([0, 500, 999, 1000, 1001, 2000, 4000], size=(m, n)).astype(np.int32)
             local = rng.integers(-100, 3000, size=m).astype(np.int32)
             req = rng.integers(0, 4500, size=m).astype(np.int32)
-            want = [ol.decide_v2(mips[q], local[q], req[q]) for q in range(m)]
-            _cache[c["id"]] = (mips, local, req, want)
-    return _cache[c["id"]]
+            want = None if decoy else [ol.decide_v2(mips[q], local[q], req[q]) for q in range(m)]
+            _cache[_key(c, decoy)] = (mips, local, req, want)
+    return _cache[_key(c, decoy)]
 
 
 TRACE_KEYS = ("arrive", "req", "mips", "dl", "ul", "init")
 
 
-def reduce_inputs(ctx, c):
+def reduce_inputs(ctx, c, decoy=False):
     """R records of generated replays (N = 8, T = 8), made once on plain tensors."""
-    if c["id"] not in _cache:
+    if _key(c, decoy) not in _cache:
         R = c["R"]
         mg, sc = fa.sweep_params(np.arange(R), 8)
-        out = fa.run_generated(ctx, 7, R, 8, 8, mg, sc, hist=False)
+        out = fa.run_generated(ctx, 8 if decoy else 7, R, 8, 8, mg, sc, hist=False)
         torch.cuda.synchronize()
-        _cache[c["id"]] = host(out.stats).view(np.int64)
-    return _cache[c["id"]]
+        _cache[_key(c, decoy)] = host(out.stats).view(np.int64)
+    return _cache[_key(c, decoy)]
+
+
+def tracegen_params(c, decoy=False):
+    mg, sc = fa.sweep_params(np.arange(7, 7 + c["R"]) + (1 if decoy else 0), c["N"])
+    return mg, sc
+
+
+def input_arrays(ctx, case: dict, decoy=False) -> dict:
+    """Every array a case's calls read, by the name of its view in the input arena (in the
+    order the views are carved)."""
+    kind = case["kind"]
+    if kind == "batch":
+        return dict(batch_inputs(case, decoy)[0])
+    if kind == "generated":
+        _, _, mg, sc, pb, pi, _ = generated_inputs(case, decoy)
+        power = dict(p_busy=pb, p_idle=pi) if pb is not None else {}
+        return dict(power, mean_gap_ticks=mg.astype(np.float64), lat_scale=sc.astype(np.int64))
+    if kind == "v2":
+        tr, broker, stop, rt, _ = v2_inputs(case, decoy)
+        return dict(tr, broker_mips=broker, stop_tick=stop, required_time_s=rt)
+    if kind == "user":
+        tr, uu, ud, _ = user_inputs(case, decoy)
+        return dict(tr, user_ul=uu, user_dl=ud)
+    if kind == "decide3":
+        busy, mips, req, _ = decide_inputs(case, decoy)
+        return dict(adv_busy=busy, adv_mips=mips, req=req)
+    if kind == "decide2":
+        mips, local, req, _ = decide_inputs(case, decoy)
+        return dict(adv_mips=mips, local_mips=local, req=req)
+    if kind == "tracegen":
+        mg, sc = tracegen_params(case, decoy)
+        return dict(mean_gap_ticks=mg.astype(np.float64), lat_scale=sc.astype(np.int64))
+    if kind == "reduce":
+        return dict(stats=reduce_inputs(ctx, case, decoy))
+    raise AssertionError(kind)
 
 
 # ---------------------------------------------------------------- the harness
@@ -249,117 +297,189 @@ def is_failed(stats: np.ndarray) -> np.ndarray:
     return ~np.isin(stats["status"], (_abi.FOGNET_OK, _abi.FOGNET_REF_ABORTED))
 
 
-def run_guarded(ctx, case: dict, poison: int, misalign: bool):
-    """Run one case with every input and every output carved from poisoned
-    arenas (inputs in one, outputs in another) on the session context; returns
-    the defined outputs as host arrays and the arenas."""
-    dev = torch.device("cuda", ctx.device)
-    ain, aout = Arena(dev, poison), Arena(dev, poison)
-    put = lambda a, name: ain.put(a, misalign, name=name)
-    new = lambda shape, dt, name: aout.alloc(shape, dt, misalign, name=name)
+class Job:
+    """One case's buffers: every input and every output a view into a poisoned arena (inputs
+    in one, outputs in another).  ``inputs``: the input views by name (``arrays``: of these
+    host arrays instead of input_arrays(ctx, case))."""
+
+    def __init__(self, ctx, case: dict, poison: int, misalign: bool, arrays: dict | None = None):
+        dev = torch.device("cuda", ctx.device)
+        self.case, self.misalign = case, misalign
+        self.ain, self.aout = Arena(dev, poison), Arena(dev, poison)
+        arrays = arrays if arrays is not None else input_arrays(ctx, case)
+        self.inputs = {k: self.ain.put(a, misalign, name=k) for k, a in arrays.items()}
+        self.out = None
+        self.hier_before = self.hier_after = None
+
+    @property
+    def arenas(self):
+        return self.ain, self.aout
+
+    def new(self, shape, dt, name):
+        return self.aout.alloc(shape, dt, self.misalign, name=name)
+
+    def records(self, n, dtype, name):
+        return records(self.aout, n, dtype, self.misalign, name)
+
+
+def build_guarded(ctx, case: dict, poison: int, misalign: bool) -> Job:
+    """Carve and fill a case's views (on the current stream; nothing of the library runs)."""
+    j = Job(ctx, case, poison, misalign)
     kind = case["kind"]
-    g: dict = {}
+    new = j.new
     if kind == "batch":
-        tr, kw, _ = batch_inputs(case)
+        tr = batch_inputs(case)[0]
         R, N, T = case["R"], case["N"], case["T"]
-        d = {k: put(v, k) for k, v in tr.items()}
         per_task = case.get("per_task", True)
-        out = fa.BatchResult(
+        j.out = fa.BatchResult(
             node=new((R, T), torch.int32, "node") if per_task else None,
             status=new((R, T), torch.uint8, "status") if per_task else None,
             start_tick=new((R, T), torch.int64, "start_tick") if per_task else None,
             done_tick=new((R, T), torch.int64, "done_tick") if per_task else None,
-            stats=records(aout, R, REP, misalign, "stats"),
+            stats=j.records(R, REP, "stats"),
             node_energy=new((R, N), torch.float64, "node_energy") if "p_busy" in tr else None,
             hist=new((_abi.HIST_METRICS, _abi.HIST_BINS), torch.int64, "hist"))
-        out.hist.zero_()  # added to: the one output the caller initialises (its bands stay poisoned)
-        before = ctx.hier_path_stats()
+        j.out.hist.zero_()  # added to: the one output the caller initialises (its bands stay poisoned)
+    elif kind == "generated":
+        R, N, T = case["R"], case["N"], case["T"]
+        j.power = (j.inputs["p_busy"], j.inputs["p_idle"]) if "p_busy" in j.inputs else None
+        j.out = fa.BatchResult(None, None, None, None, stats=j.records(R, REP, "stats"),
+                               node_energy=new((R, N), torch.float64, "node_energy") if j.power else None,
+                               hist=new((_abi.HIST_METRICS, _abi.HIST_BINS), torch.int64, "hist"))
+        j.out.hist.zero_()
+    elif kind == "v2":
+        R, T = case["R"], case["T"]
+        j.out = fa.V2Result(new((R, T), torch.int32, "node"), new((R, T), torch.uint8, "status"),
+                            new((R, T), torch.int64, "start_tick"), new((R, T), torch.int64, "done_tick"),
+                            j.records(R, V2, "stats"))
+    elif kind == "user":
+        R, T = j.inputs["arrive"].shape
+        j.out = fa.BatchResult(new((R, T), torch.int32, "node"), new((R, T), torch.uint8, "status"),
+                               new((R, T), torch.int64, "start_tick"), new((R, T), torch.int64, "done_tick"),
+                               stats=j.records(R, REP, "stats"))
+        j.res = j.records(R, USER, "user_stats")
+    elif kind == "decide3":
+        j.out = (new(case["m"], torch.int32, "node"), new(case["m"], torch.int32, "status"))
+    elif kind == "decide2":
+        j.out = (new(case["m"], torch.int32, "action"), new(case["m"], torch.int32, "node"))
+    elif kind == "tracegen":
+        R, N, T = case["R"], case["N"], case["T"]
+        dts = dict(arrive=torch.int64, req=torch.int32, mips=torch.int32, dl=torch.int64, ul=torch.int64,
+                   init=torch.int64)  # fa.allocate_trace's layout
+        j.out = {k: new((R, T) if k in ("arrive", "req") else (R, N), dts[k], k) for k in TRACE_KEYS}
+    elif kind == "reduce":
+        j.job_buf = j.records(1, JOB, "job")
+    else:
+        raise AssertionError(kind)
+    return j
+
+
+def enqueue_user_stats(ctx, d: dict, out, user_ul, user_dl, res):
+    """fognet_user_stats_dev with the caller's buffers and nothing else (fa.user_stats, which
+    reads the records back, waits for them)."""
+    R, T = d["arrive"].shape
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    bi = _abi.BatchIn(R, T, d["mips"].shape[-1], out.policy, d["mips"].shape[-1] if d["mips"].dim() == 2 else 0, 0,
+                      p(d["arrive"]), p(d["req"]), p(d["mips"]), p(d["dl"]), p(d["ul"]), p(d["init"]),
+                      None, None, None, None, 0)
+    bo = _abi.BatchOut(p(out.node), p(out.status), p(out.start_tick), p(out.done_tick), p(out.stats), None, None, None)
+    s = C.c_void_p(torch.cuda.current_stream(res.device).cuda_stream)
+    ctx.check(ctx._lib.fognet_user_stats_dev(ctx.handle, C.byref(bi), C.byref(bo), p(user_ul), p(user_dl),
+                                             1 if user_ul.dim() == 2 else 0, p(res), s), "user_stats")
+
+
+def call_guarded(ctx, j: Job, enqueue_only: bool = False):
+    """The case's library calls on the current stream.  ``enqueue_only``: where a wrapper ends by
+    reading its result back (fa.user_stats, fa.reduce_stats), the entry point itself is called
+    with the same buffers, so that nothing here waits for the device."""
+    case, d, out = j.case, j.inputs, j.out
+    kind = case["kind"]
+    if kind == "batch":
+        kw = batch_inputs(case)[1]
+        j.hier_before = ctx.hier_path_stats()
         if case.get("separate"):
             fa.run_batch(ctx, d, out=out, stage="replay", **kw)
             fa.run_batch(ctx, d, out=out, stage="stats", **kw)
         else:
             fa.run_batch(ctx, d, out=out, **kw)
-        torch.cuda.synchronize()
-        after = ctx.hier_path_stats()
+        j.hier_after = ctx.hier_path_stats()
+    elif kind == "generated":
+        seed, r0 = generated_inputs(case)[:2]
+        fa.run_generated(ctx, seed, case["R"], case["T"], case["N"], d["mean_gap_ticks"], d["lat_scale"], r0=r0,
+                         out=out, power=j.power)
+    elif kind == "v2":
+        fa.run_v2(ctx, d, d["broker_mips"], d["stop_tick"], d["required_time_s"], queue_capacity=4096, out=out)
+    elif kind == "user":
+        fa.run_batch(ctx, d, out=out)
+        if enqueue_only:
+            enqueue_user_stats(ctx, d, out, d["user_ul"], d["user_dl"], j.res)
+        else:
+            j.user = fa.user_stats(ctx, d, out, d["user_ul"], d["user_dl"], res=j.res)
+    elif kind == "decide3":
+        fa.BrokerBaseApp3(ctx).sendPubAck_batch(d["adv_busy"], d["adv_mips"], d["req"], out=out)
+    elif kind == "decide2":
+        fa.BrokerBaseApp2(ctx).sendPubAck_batch(d["adv_mips"], d["local_mips"], d["req"], out=out)
+    elif kind == "tracegen":
+        fa.generate_trace(ctx, 0x5EED0003, case["R"], case["T"], case["N"], d["mean_gap_ticks"], d["lat_scale"],
+                          r0=7, out=out)
+    elif kind == "reduce":
+        stats = d["stats"].view(torch.uint8)
+        if enqueue_only:
+            s = C.c_void_p(torch.cuda.current_stream(stats.device).cuda_stream)
+            ctx.check(ctx._lib.fognet_reduce_stats_dev(ctx.handle, C.c_void_p(stats.data_ptr()), case["R"],
+                                                       C.c_void_p(j.job_buf.data_ptr()), s), "reduce_stats")
+        else:
+            j.job = fa.reduce_stats(ctx, stats, case["R"], out=j.job_buf)
+    else:
+        raise AssertionError(kind)
+
+
+def collect_guarded(ctx, j: Job) -> dict:
+    """The defined outputs as host arrays, once the calls have finished."""
+    case, out = j.case, j.out
+    kind = case["kind"]
+    if kind == "batch":
         g = dict(stats=host(out.stats).view(REP), hist=host(out.hist),
                  energy=host(out.node_energy) if out.node_energy is not None else None,
-                 hier_launches=(after[0] - before[0], after[1] - before[1]))
-        if per_task:
+                 hier_launches=(j.hier_after[0] - j.hier_before[0], j.hier_after[1] - j.hier_before[1]))
+        if case.get("per_task", True):
             g.update(node=host(out.node), status=host(out.status), start=host(out.start_tick), done=host(out.done_tick))
         blank_undefined(g, is_failed(g["stats"]))
     elif kind == "generated":
-        seed, r0, mg, sc, pb, pi, _ = generated_inputs(case)
-        R, N, T = case["R"], case["N"], case["T"]
-        power = (put(pb, "p_busy"), put(pi, "p_idle")) if pb is not None else None
-        out = fa.BatchResult(None, None, None, None, stats=records(aout, R, REP, misalign, "stats"),
-                             node_energy=new((R, N), torch.float64, "node_energy") if power else None,
-                             hist=new((_abi.HIST_METRICS, _abi.HIST_BINS), torch.int64, "hist"))
-        out.hist.zero_()
-        fa.run_generated(ctx, seed, R, T, N, put(mg.astype(np.float64), "mean_gap_ticks"),
-                         put(sc.astype(np.int64), "lat_scale"), r0=r0, out=out, power=power)
-        torch.cuda.synchronize()
         g = dict(stats=host(out.stats).view(REP), hist=host(out.hist),
-                 energy=host(out.node_energy) if power else None)
+                 energy=host(out.node_energy) if j.power else None)
     elif kind == "v2":
-        tr, broker, stop, rt, _ = v2_inputs(case)
-        R, T = case["R"], case["T"]
-        d = {k: put(v, k) for k, v in tr.items()}
-        out = fa.V2Result(new((R, T), torch.int32, "node"), new((R, T), torch.uint8, "status"),
-                          new((R, T), torch.int64, "start_tick"), new((R, T), torch.int64, "done_tick"),
-                          records(aout, R, V2, misalign, "stats"))
-        fa.run_v2(ctx, d, put(broker, "broker_mips"), put(stop, "stop_tick"), put(rt, "required_time_s"),
-                  queue_capacity=4096, out=out)
-        torch.cuda.synchronize()
         g = dict(node=host(out.node), status=host(out.status), start=host(out.start_tick), done=host(out.done_tick),
                  stats=host(out.stats).view(V2))
         blank_undefined(g, g["stats"]["status"] != _abi.FOGNET_OK)
     elif kind == "user":
-        tr, uu, ud, _ = user_inputs(case)
-        R, T = tr["arrive"].shape
-        d = {k: put(v, k) for k, v in tr.items()}
-        out = fa.BatchResult(new((R, T), torch.int32, "node"), new((R, T), torch.uint8, "status"),
-                             new((R, T), torch.int64, "start_tick"), new((R, T), torch.int64, "done_tick"),
-                             stats=records(aout, R, REP, misalign, "stats"))
-        fa.run_batch(ctx, d, out=out)
-        res = records(aout, R, USER, misalign, "user_stats")
-        user = fa.user_stats(ctx, d, out, put(uu, "user_ul"), put(ud, "user_dl"), res=res)
-        torch.cuda.synchronize()
-        g = dict(user=user.copy(), user_bytes=host(res), stats=host(out.stats).view(REP))
+        user = getattr(j, "user", None)
+        g = dict(user=user.copy() if user is not None else host(j.res).view(USER), user_bytes=host(j.res),
+                 stats=host(out.stats).view(REP))
     elif kind == "decide3":
-        busy, mips, req, _ = decide_inputs(case)
-        node, status = new(case["m"], torch.int32, "node"), new(case["m"], torch.int32, "status")
-        fa.BrokerBaseApp3(ctx).sendPubAck_batch(put(busy, "adv_busy"), put(mips, "adv_mips"), put(req, "req"),
-                                                out=(node, status))
-        torch.cuda.synchronize()
-        g = dict(node=host(node), status=host(status))
+        g = dict(node=host(out[0]), status=host(out[1]))
     elif kind == "decide2":
-        mips, local, req, _ = decide_inputs(case)
-        act, node = new(case["m"], torch.int32, "action"), new(case["m"], torch.int32, "node")
-        fa.BrokerBaseApp2(ctx).sendPubAck_batch(put(mips, "adv_mips"), put(local, "local_mips"), put(req, "req"),
-                                                out=(act, node))
-        torch.cuda.synchronize()
-        g = dict(action=host(act), node=host(node))
+        g = dict(action=host(out[0]), node=host(out[1]))
     elif kind == "tracegen":
-        R, N, T = case["R"], case["N"], case["T"]
-        mg, sc = fa.sweep_params(np.arange(7, 7 + R), N)
-        dts = dict(arrive=torch.int64, req=torch.int32, mips=torch.int32, dl=torch.int64, ul=torch.int64,
-                   init=torch.int64)  # fa.allocate_trace's layout
-        tr = {k: new((R, T) if k in ("arrive", "req") else (R, N), dts[k], k) for k in TRACE_KEYS}
-        fa.generate_trace(ctx, 0x5EED0003, R, T, N, put(mg.astype(np.float64), "mean_gap_ticks"),
-                          put(sc.astype(np.int64), "lat_scale"), r0=7, out=tr)
-        torch.cuda.synchronize()
-        g = {k: host(tr[k]) for k in TRACE_KEYS}
-        g["params"] = (mg, sc)
+        g = {k: host(out[k]) for k in TRACE_KEYS}
+        g["params"] = tracegen_params(case)
     elif kind == "reduce":
-        recs = reduce_inputs(ctx, case)
-        stats = put(recs, "stats").view(torch.uint8)
-        job_buf = records(aout, 1, JOB, misalign, "job")
-        job = fa.reduce_stats(ctx, stats, case["R"], out=job_buf)
-        torch.cuda.synchronize()
-        g = dict(job=job.copy(), job_bytes=host(job_buf), reps=recs.view(REP))
+        job = getattr(j, "job", None)
+        g = dict(job=job.copy() if job is not None else host(j.job_buf).view(JOB)[0], job_bytes=host(j.job_buf),
+                 reps=reduce_inputs(ctx, case).view(REP))
     else:
         raise AssertionError(kind)
-    return g, (ain, aout)
+    return g
+
+
+def run_guarded(ctx, case: dict, poison: int, misalign: bool):
+    """Run one case with every input and every output carved from poisoned
+    arenas (inputs in one, outputs in another) on the session context; returns
+    the defined outputs as host arrays and the arenas."""
+    j = build_guarded(ctx, case, poison, misalign)
+    call_guarded(ctx, j)
+    torch.cuda.synchronize()
+    return collect_guarded(ctx, j), j.arenas
 
 
 # ---------------------------------------------------------------- (b): the oracle
