@@ -139,6 +139,12 @@ class BatchOut(C.Structure):
                 ("hist", C.c_void_p), ("escalated", C.c_void_p)]
 
 
+class SignalVectors(C.Structure):
+    """fognet_signal_vectors: one CSR per replication (device pointers)."""
+    _fields_ = [("cap", C.c_int64), ("offset", C.c_void_p), ("time", C.c_void_p), ("value", C.c_void_p),
+                ("task", C.c_void_p)]
+
+
 class GenParams(C.Structure):
     _fields_ = [("seed", C.c_uint32), ("req_lo", C.c_int32), ("req_hi", C.c_int32), ("pad", C.c_int32),
                 ("mean_gap_ticks", C.c_void_p), ("lat_scale", C.c_void_p)]
@@ -210,6 +216,8 @@ SIGNATURES = {
     "fognet_per_user_stats_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P, C.c_int32, C.c_int32,
                                             P, P, P, P, P]),
     "fognet_reduce_user_stats_dev": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, P]),
+    "fognet_signal_vectors_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P, C.c_int32, C.c_int32,
+                                            P, P, C.c_int32, C.c_int32, C.POINTER(SignalVectors), P, P]),
     "fognet_user_stats_init": (None, [C.POINTER(UserStats)]),
     "fognet_user_stats_merge": (None, [C.POINTER(UserStats), C.POINTER(UserStats)]),
     "fognet_job_stats_init": (None, [C.POINTER(JobStats)]),
@@ -234,6 +242,8 @@ SIGNATURES = {
     "fognet_write_sca_nodes": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int]),
     "fognet_write_sca_users": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int]),
     "fognet_write_vec": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P, P, P, P, P, P]),
+    "fognet_write_vec_users": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P, P, P, P,
+                                         C.c_int]),
     "fognet_gen_trace_mqtt": (C.c_int, [C.c_uint32, C.c_int32, P, P, P, P, C.c_int64, C.c_int32, C.c_int32,
                                         C.c_int32, P, P, P, C.POINTER(C.c_int32)]),
 }

@@ -870,6 +870,57 @@ int fognet_per_user_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fo
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "per-user stats launch");
 }
 
+int fognet_signal_vectors_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out,
+                              const int32_t* user_of, int32_t U, int32_t link_stride, const int64_t* user_ul,
+                              const int64_t* user_dl, int32_t r0, int32_t Rv, const fognet_signal_vectors* vec,
+                              int64_t* n_unassigned, void* stream) {
+  if (!c || !out) return FOGNET_ERR_ARG;
+  if (in && in->policy == FOGNET_POLICY_EXT_HIER)
+    return fail(c, FOGNET_ERR_UNSUPPORTED,
+                "signal vectors under EXT_HIER: where an escalated task's acks stand among the acks of their tick is "
+                "builder-defined, and no recording of the reference pins it");
+  fognet::ReplayArgs a;
+  int rc = prepare(c, in, &a);
+  if (rc) return rc;
+  if (U < 0) return fail(c, FOGNET_ERR_ARG, "negative U");
+  if (link_stride != 0 && link_stride != U) return fail(c, FOGNET_ERR_ARG, "link_stride must be 0 or U");
+  if (r0 < 0 || Rv < 0 || (int64_t)r0 + Rv > a.R) return fail(c, FOGNET_ERR_ARG, "[r0, r0 + Rv) must lie in [0, R)");
+  if (Rv == 0) return FOGNET_OK;
+  if (!out->stats) return fail(c, FOGNET_ERR_ARG, "null stats");
+  if (a.T > 0 && (!out->node || !out->status || !out->start_tick || !out->done_tick))
+    return fail(c, FOGNET_ERR_ARG, "signal vectors need the per-task outputs, start_tick included");
+  if (a.T > 0 && !user_of) return fail(c, FOGNET_ERR_ARG, "null user_of");
+  if (U > 0 && (!user_ul || !user_dl)) return fail(c, FOGNET_ERR_ARG, "null user links");
+  if (!vec || !vec->offset || (a.T > 0 && (!vec->time || !vec->value || !vec->task)))
+    return fail(c, FOGNET_ERR_ARG, "null vec or vec arrays");
+  if (vec->cap < 6 * (int64_t)a.T) return fail(c, FOGNET_ERR_ARG, "vec->cap must be at least 6 * T");
+  const int64_t V = (int64_t)a.N + 1 + 3 * (int64_t)U;
+  if (a.T >= (1 << 28) || V * Rv >= ((int64_t)1 << 31))
+    return fail(c, FOGNET_ERR_UNSUPPORTED, "signal vectors: T >= 2^28 or Rv * V >= 2^31");
+  rc = set_device(c);
+  if (rc) return rc;
+  fognet::VecWs w{};
+  fognet::WsCursor measure{nullptr};
+  rc = ensure(c, (void**)&c->ring, &c->ring_bytes, fognet::signal_vectors_ws(w, (size_t)Rv, (size_t)V, measure),
+              "signal vector cursors");
+  if (rc) return rc;
+  fognet::WsCursor carve{reinterpret_cast<unsigned char*>(c->ring)};
+  (void)fognet::signal_vectors_ws(w, (size_t)Rv, (size_t)V, carve);
+  a.out_node = out->node;
+  a.out_status = out->status;
+  a.out_start = out->start_tick;
+  a.out_done = out->done_tick;
+  a.out_stats = out->stats;
+  // FOGNET_VEC_SORT=hbm: every segment is sorted in HBM and the counters live in HBM (the layouts of
+  // large segments and of V > signal_vectors_lds_max()), so small tests run both on the same traces.
+  // FOGNET_VEC_STAGES=1 / 2: stop after the count / place stage (tools/time_signal_vectors.py).
+  const int stages = env_is("FOGNET_VEC_STAGES", "1") ? 1 : env_is("FOGNET_VEC_STAGES", "2") ? 2 : 3;
+  const hipError_t e = fognet::launch_signal_vectors(a, user_of, U, link_stride, user_ul, user_dl, r0, Rv, *vec,
+                                                     n_unassigned, w.cursor, env_is("FOGNET_VEC_SORT", "hbm"), stages,
+                                                     (hipStream_t)stream);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "signal vectors launch");
+}
+
 int fognet_reduce_user_stats_dev(fognet_ctx* c, const fognet_user_stats* user_stats, const fognet_rep_stats* stats,
                                  int32_t R, int32_t U, fognet_user_stats* out, void* stream) {
   if (!c) return FOGNET_ERR_ARG;

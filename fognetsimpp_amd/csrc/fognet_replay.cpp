@@ -334,7 +334,7 @@ struct Options {
   int nodes = 0, reps = 1, device = 0, ring = 0;
   uint32_t seed = 1;
   int64_t dl = kMs, ul = kMs, user_ul = kMs, user_dl = kMs, stop = kNoTick;
-  bool user_dl_set = false, dry_run = false, policy_set = false, quiet = false, show = false, node_stats = false, user_stats = false;
+  bool user_dl_set = false, dry_run = false, policy_set = false, quiet = false, show = false, node_stats = false, user_stats = false, vec_users = false;
   int policy = FOGNET_POLICY_REF_V3;
   double p_busy = -1.0, p_idle = -1.0;
 };
@@ -476,6 +476,8 @@ void usage() {
       "  --ring N             per-node pending capacity (power of two)\n"
       "  --trace-out FILE     write the FOGNTRC1 trace  --sca FILE / --vec FILE (replication 0)\n"
       "  --node-stats         with --sca: append one block per fog node (tasks, queueTime, response)\n"
+      "  --vec-users          with --vec (BrokerBaseApp3 runs from an ini): append replication 0's delay vector and\n"
+      "                       every user module's latency, latencyH1 and taskTime vectors, in emission order\n"
       "  --user-stats         with --sca (BrokerBaseApp3 runs from an ini): append one block per user module\n"
       "                       (latency, latencyH1, taskTime) and the broker's delay\n"
       "  --device D           HIP device (default 0)\n"
@@ -533,6 +535,7 @@ Options parse_args(int argc, char** argv) {
     else if (a == "--show") o.show = true;
     else if (a == "--node-stats") o.node_stats = true;
     else if (a == "--user-stats") o.user_stats = true;
+    else if (a == "--vec-users") o.vec_users = true;
     else if (a == "--world") o.world = (int)parse_int(need(i), "--world");
     else if (a == "--rank") o.rank = (int)parse_int(need(i), "--rank");
     else if (a == "--comm-id") o.comm_id = need(i);
@@ -549,6 +552,9 @@ Options parse_args(int argc, char** argv) {
   if (o.user_stats && o.world > 1) die("--user-stats: the per-user records of several ranks are not combined (--world 1)");
   if (o.user_stats && !o.trace_in.empty()) die("--user-stats needs the ini's user modules (-f INI): a trace file names no users");
   if (o.user_stats && o.user_dl < 0) die("--user-stats needs a broker->user latency (--user-dl none gives the acks no way back)");
+  if (o.vec_users && o.vec.empty()) die("--vec-users appends to replication 0's .vec: give --vec FILE");
+  if (o.vec_users && !o.trace_in.empty()) die("--vec-users needs the ini's user modules (-f INI): a trace file names no users");
+  if (o.vec_users && o.user_dl < 0) die("--vec-users needs a broker->user latency (--user-dl none gives the acks no way back)");
   if (o.world > 1 && o.comm_id.empty()) die("--world > 1 needs --comm-id FILE (the communicator id's rendezvous)");
   if (o.reps < o.world) die("--reps must be >= --world (every rank replays a block of replications)");
   if (o.ring != 0 && (o.ring < 2 || o.ring > (1 << 15) || (o.ring & (o.ring - 1)) != 0))
@@ -733,6 +739,51 @@ void append_user_stats(const Options& o, fognet_ctx* ctx, const fognet_batch_in&
         "sca users");
 }
 
+// --vec-users: replication 0's user-side vectors (fognet_signal_vectors_dev over device copies of the trace,
+// the per-task outputs and user_of, with the links --user-ul / --user-dl shared by all users), appended to the
+// .vec fognet_write_vec wrote: the broker's delay and every user module's latency, latencyH1 and taskTime.
+void append_user_vectors(const Options& o, fognet_ctx* ctx, const fognet_batch_in& in, const fognet_batch_out& out,
+                         const UserSide& us, const std::string& network, const std::string& run_id) {
+  const size_t R = (size_t)in.R, RT = R * (size_t)in.T, N = (size_t)in.N, NRN = (in.node_stride ? R : 1) * N;
+  const int32_t U = (int32_t)us.modules.size();
+  const size_t V = N + 1 + 3 * (size_t)U, cap = 6 * (size_t)in.T;
+  auto up = [](const auto* h, size_t n) {
+    return dev_copy(std::vector<std::remove_cv_t<std::remove_pointer_t<decltype(h)>>>(h, h + n));
+  };
+  fognet_batch_in din = in;
+  din.arrive_tick = up(in.arrive_tick, RT), din.req_mips = up(in.req_mips, RT), din.mips = up(in.mips, NRN);
+  din.dl_tick = up(in.dl_tick, NRN), din.ul_tick = up(in.ul_tick, NRN), din.init_adv_tick = up(in.init_adv_tick, NRN);
+  din.p_busy_w = din.p_idle_w = nullptr;
+  din.down_tick = nullptr;
+  fognet_batch_out dout{up(out.node, RT), up(out.status, RT), up(out.start_tick, RT), up(out.done_tick, RT),
+                        up(out.stats, R), nullptr, nullptr};
+  int32_t* d_user_of = dev_copy(us.user_of);
+  int64_t* d_ul = dev_copy(std::vector<int64_t>(U, o.user_ul));
+  int64_t* d_dl = dev_copy(std::vector<int64_t>(U, o.user_dl));
+  fognet_signal_vectors vec{(int64_t)cap, dev_alloc<int64_t>(V + 1), dev_alloc<int64_t>(cap), dev_alloc<int64_t>(cap),
+                            dev_alloc<int32_t>(cap)};
+  int64_t* d_un = dev_alloc<int64_t>(1);
+  check_ctx(ctx, fognet_signal_vectors_dev(ctx, &din, &dout, d_user_of, U, 0, d_ul, d_dl, 0, 1, &vec, d_un, nullptr),
+            "fognet_signal_vectors_dev");
+  std::vector<int64_t> offset(V + 1), time(cap), value(cap);
+  int64_t un = 0;
+  hip_check(hipMemcpy(offset.data(), vec.offset, (V + 1) * sizeof(int64_t), hipMemcpyDeviceToHost), "hipMemcpy");
+  hip_check(hipMemcpy(time.data(), vec.time, cap * sizeof(int64_t), hipMemcpyDeviceToHost), "hipMemcpy");
+  hip_check(hipMemcpy(value.data(), vec.value, cap * sizeof(int64_t), hipMemcpyDeviceToHost), "hipMemcpy");
+  hip_check(hipMemcpy(&un, d_un, sizeof un, hipMemcpyDeviceToHost), "hipMemcpy");
+  const void* bufs[] = {din.arrive_tick, din.req_mips, din.mips, din.dl_tick, din.ul_tick, din.init_adv_tick, dout.node,
+                        dout.status, dout.start_tick, dout.done_tick, dout.stats, d_user_of, d_ul, d_dl, vec.offset,
+                        vec.time, vec.value, vec.task, d_un};
+  for (const void* b : bufs) (void)hipFree(const_cast<void*>(b));
+  if (un != 0) die("--vec-users: replication 0 has " + std::to_string(un) + " publishes of no known user");
+  std::vector<const char*> names(U);
+  for (int32_t u = 0; u < U; ++u) names[u] = us.modules[u].c_str();
+  // after fognet_write_vec's ids: 0 = decisions, 1 + j = node j's queueTime
+  check(fognet_write_vec_users(o.vec.c_str(), run_id.c_str(), network.c_str(), U, in.N + 1, offset.data() + N, time.data(),
+                               value.data(), names.data(), 1),
+        "vec users");
+}
+
 int run_v3(const Options& o, fognet_batch_in in, const std::string& network, const std::string& run_id,
            const UserSide* us = nullptr) {
   const size_t RT = (size_t)in.R * (size_t)in.T;
@@ -782,6 +833,7 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
     check(fognet_write_vec(o.vec.c_str(), run_id.c_str(), network.c_str(), in.T, in.N, in.arrive_tick, in.dl_tick,
                            node.data(), status.data(), start.data(), nullptr),
           "vec");
+    if (o.vec_users && us) append_user_vectors(o, ctx, in, out, *us, network, run_id);
   }
   if (!o.quiet) {
     std::printf("policy=%s R=%d T=%d N=%d decisions=%" PRId64 " queued=%" PRId64 " started=%" PRId64
@@ -932,6 +984,8 @@ int main(int argc, char** argv) {
   if (v2 && o.policy_set) die("--policy applies to BrokerBaseApp3 runs");
   if (v2 && o.user_stats)
     die("--user-stats applies to BrokerBaseApp3 runs (the BrokerBaseApp2 model has no closed form for the user signals)");
+  if (v2 && o.vec_users)
+    die("--vec-users applies to BrokerBaseApp3 runs (the BrokerBaseApp2 model has no closed form for the user signals)");
   const int32_t N = (int32_t)sc.mips.size();
   // BrokerBaseApp2 does not answer a user's CONNECT with a CONNACK, so its
   // users publish from startTime + sendInterval on
@@ -943,7 +997,7 @@ int main(int argc, char** argv) {
   const int r0 = o.rank * q + std::min(o.rank, rem), nr = q + (o.rank < rem ? 1 : 0);
   UserSide us;
   us.modules = sc.users;
-  const int32_t T = gen_traces(sc, o, user_dl, r0, nr, arrive, req, o.user_stats ? &us.user_of : nullptr);
+  const int32_t T = gen_traces(sc, o, user_dl, r0, nr, arrive, req, o.user_stats || o.vec_users ? &us.user_of : nullptr);
 
   // node k: CONNECT at startTime reaches the broker after ul, the CONNACK
   // comes back after dl, the first ADVERTISEMIPS fires 0.01 s later
@@ -1009,5 +1063,5 @@ int main(int argc, char** argv) {
     if (o.world > 1) die("BrokerBaseApp2 replays run on one GPU (--world 1)");
     return run_v2(o, sc, T, arrive, req, dl, ul, first_adv, run_id);
   }
-  return run_v3(o, in, sc.network, run_id, o.user_stats ? &us : nullptr);
+  return run_v3(o, in, sc.network, run_id, o.user_stats || o.vec_users ? &us : nullptr);
 }

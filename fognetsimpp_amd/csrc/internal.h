@@ -439,6 +439,16 @@ hipError_t launch_per_user_stats(const ReplayArgs& a, const int32_t* user_of, in
                                  int64_t* n_unassigned, bool force_hbm, hipStream_t s);
 hipError_t launch_reduce_user_stats(const fognet_user_stats* in, const fognet_rep_stats* stats, int32_t R, int32_t U,
                                     fognet_user_stats* out, hipStream_t s);
+// Signal vectors of a finished replay (signal_vectors.hip): count, place, order.  Up to
+// signal_vectors_lds_max() vectors the counts and cursors live in LDS, and a segment of up to
+// signal_vectors_sort_lds_max() rows is sorted in LDS, unless force_hbm; cursor: the workspace's
+// [Rv][V] cursors (VecWs).  stages: 1 stops after count, 2 after place (timing), 3: the whole pass.
+int32_t signal_vectors_lds_max();
+int32_t signal_vectors_sort_lds_max();
+hipError_t launch_signal_vectors(const ReplayArgs& a, const int32_t* user_of, int32_t U, int32_t link_stride,
+                                 const int64_t* user_ul, const int64_t* user_dl, int32_t r0, int32_t Rv,
+                                 const fognet_signal_vectors& vec, int64_t* n_unassigned, uint32_t* cursor,
+                                 bool force_hbm, int stages, hipStream_t s);
 // v2 model replay (replay_v2.hip)
 size_t replay_v2_workspace_bytes(int32_t R, int32_t T, int32_t N, int32_t q_log2);
 hipError_t launch_replay_v2(const fognet_v2_in& in, const fognet_v2_out& out, void* workspace, int32_t q_log2,

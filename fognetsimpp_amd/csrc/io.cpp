@@ -587,6 +587,45 @@ int fognet_write_vec(const char* path, const char* run_id, const char* network, 
   return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_vec: write failed: ") + path);
 }
 
+int fognet_write_vec_users(const char* path, const char* run_id, const char* network, int32_t U, int32_t id_base,
+                           const int64_t* offset, const int64_t* time, const int64_t* value,
+                           const char* const* user_module, int append) {
+  if (!path || !run_id || !network || U < 0 || id_base < 0 || !offset)
+    return fail(FOGNET_ERR_ARG, "write_vec_users: bad argument");
+  const int32_t nv = 1 + 3 * U;  // delay, U x latency, U x latencyH1, U x taskTime
+  for (int32_t v = 0; v < nv; ++v)
+    if (offset[v] < 0 || offset[v + 1] < offset[v]) return fail(FOGNET_ERR_ARG, "write_vec_users: offsets must be nondecreasing");
+  if (offset[nv] > offset[0] && (!time || !value)) return fail(FOGNET_ERR_ARG, "write_vec_users: null array");
+  if (user_module)
+    for (int32_t u = 0; u < U; ++u)
+      if (!user_module[u]) return fail(FOGNET_ERR_ARG, "write_vec_users: null module name");
+  FILE* f = fopen(path, append ? "a" : "w");
+  if (!f) return fail(FOGNET_ERR_ARG, std::string("write_vec_users: cannot open ") + path);
+  if (!append) run_header(f, run_id, network);
+  // vector ids: id_base = the broker's delay, id_base + 1 + 3 u + {0, 1, 2} = user u's latency, latencyH1, taskTime
+  const char* names[3] = {"latency", "latencyH1", "taskTime"};
+  auto declare = [&](int32_t id, const std::string& mod, const char* name) {
+    fprintf(f, "vector %d  %s  %s:vector  TV\n", id, mod.c_str(), name);
+    fprintf(f, "attr interpolationmode  none\nattr source  %s\nattr title  \"%s, vector\"\n", name, name);
+  };
+  declare(id_base, std::string(network) + ".broker.udpApp[0]", "delay");
+  for (int32_t u = 0; u < U; ++u) {
+    const std::string mod = std::string(network) + "." +
+                            (user_module ? std::string(user_module[u]) : "user[" + std::to_string(u) + "]") + ".udpApp[0]";
+    for (int s = 0; s < 3; ++s) declare(id_base + 1 + 3 * u + s, mod, names[s]);
+  }
+  // rows in the order of the CSR; the recorded value is raw * 1e-12 (delay: s, the user signals: ms)
+  auto rows = [&](int32_t id, int32_t v) {
+    for (int64_t p = offset[v]; p < offset[v + 1]; ++p)
+      fprintf(f, "%d\t%s\t%s\n", id, simtime_str(time[p]).c_str(), num((double)value[p] * 1e-12).c_str());
+  };
+  rows(id_base, 0);
+  for (int32_t u = 0; u < U; ++u)
+    for (int s = 0; s < 3; ++s) rows(id_base + 1 + 3 * u + s, 1 + s * U + u);
+  const bool ok = ferror(f) == 0;
+  return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_vec_users: write failed: ") + path);
+}
+
 int fognet_gen_trace_mqtt(uint32_t seed, int32_t U, const int64_t* start_tick, const int64_t* interval_tick,
                           const int64_t* uplink_tick, const int64_t* downlink_tick, int64_t stop_tick,
                           int32_t req_base, int32_t req_span, int32_t cap, int64_t* arrive_tick, int32_t* req_mips,

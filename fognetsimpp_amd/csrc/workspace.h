@@ -83,4 +83,16 @@ size_t region_ws(ReplayWs& h, W& w, size_t R, size_t T, size_t N, size_t B, size
   return resume || v.end > o_end ? v.end : o_end;
 }
 
+// Signal vectors (signal_vectors.hip): [cursors].  One 32-bit cursor per (replication, vector) of the
+// place kernel, which zeroes its replication's row itself; used only above the kernel's LDS capacity
+// (or when the HBM layouts are forced), but sized for every call so the layout has one form.
+struct VecWs {
+  uint32_t* cursor;  // [Rv][V] rows placed so far in each vector's segment
+};
+
+inline size_t signal_vectors_ws(VecWs& w, size_t Rv, size_t V, WsCursor& v) {
+  v(w.cursor, Rv * V);
+  return v.off;
+}
+
 }  // namespace fognet

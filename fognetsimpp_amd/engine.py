@@ -566,6 +566,74 @@ def per_user_stats(ctx: Context, trace: dict, out: BatchResult, user_of, user_ul
     return res[:nres].view(R, U * _abi.USER_STATS_DTYPE.itemsize), un
 
 
+def signal_vectors(ctx: Context, trace: dict, out: BatchResult, user_of, user_ul, user_dl, r0: int = 0,
+                   Rv: int | None = None, policy: str | int | None = None, bufs: dict | None = None,
+                   allow_unassigned: bool = False, to_host: bool = True) -> dict:
+    """The recorded signals of replications [r0, r0 + Rv) of a finished replay as ordered
+    vectors (fognet_signal_vectors_dev), on the current stream: per replication one CSR over
+    V = N + 1 + 3U vectors (the N nodes' ``queueTime``, the broker's ``delay``, U x ``latency``,
+    U x ``latencyH1``, U x ``taskTime``), every vector in the order the module made the
+    emissions (include/fognet_hip.h "Signal vectors").  ``user_of`` / ``user_ul`` /
+    ``user_dl``: as :func:`per_user_stats`.  Returns numpy arrays: ``offset`` int64 [Rv, V + 1],
+    ``time`` / ``value`` int64 [Rv, 6T] (ticks; raw values in the records' units), ``task``
+    int32 [Rv, 6T] and ``n_unassigned`` int64 [Rv]; vector v of replication q is
+    ``[offset[q, v], offset[q, v + 1])``, and what lies at and past ``offset[q, V]`` is
+    unwritten memory.  ``bufs``: device tensors ``offset`` / ``time`` / ``value`` / ``task`` /
+    ``n_unassigned`` of those shapes to write into.  ``to_host=False``: the call only enqueues
+    and returns the device tensors instead (no copy back, no check of ``n_unassigned``).  A
+    non-zero ``n_unassigned`` raises FognetError (FOGNET_ERR_ARG) unless ``allow_unassigned``.  ``policy``: the replay's (None: what run_batch recorded on ``out``);
+    "REF_V3" and "EXT_LAT"; "EXT_HIER" is refused (FOGNET_ERR_UNSUPPORTED, nothing written)."""
+    arrive = trace["arrive"]
+    R, T = arrive.shape
+    dev = arrive.device
+    Rv = R - r0 if Rv is None else Rv
+
+    def on_dev(x, dt):
+        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        return t.to(device=dev, dtype=dt).contiguous()
+    uo, uu, ud = on_dev(user_of, torch.int32), on_dev(user_ul, torch.int64), on_dev(user_dl, torch.int64)
+    if tuple(uo.shape) != (R, T):
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"user_of must have shape [R, T], got {tuple(uo.shape)}")
+    U = uu.shape[-1] if uu.dim() else -1
+    if uu.shape != ud.shape or tuple(uu.shape) not in ((U,), (R, U)):
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"user links must both have shape [U] or [R, U], got "
+                                               f"{tuple(uu.shape)} / {tuple(ud.shape)}")
+    mips = trace["mips"]
+    N = mips.shape[-1]
+    V, cap, rows = N + 1 + 3 * U, 6 * T, max(Rv, 0)
+    shapes = dict(offset=((rows, V + 1), torch.int64), time=((rows, cap), torch.int64), value=((rows, cap), torch.int64),
+                  task=((rows, cap), torch.int32), n_unassigned=((rows,), torch.int64))
+    b = dict(bufs or {})
+    for k, (shape, dt) in shapes.items():
+        if b.get(k) is None:
+            b[k] = torch.empty(shape, dtype=dt, device=dev)
+        t = b[k]
+        if t.dtype != dt or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            raise FognetError(_abi.FOGNET_ERR_ARG, f"signal_vectors: {k} must be a contiguous {dt} tensor of shape "
+                                                   f"{shape} on the trace's device")
+    if policy is None:
+        policy = out.policy if out.policy is not None else _abi.FOGNET_POLICY_REF_V3
+    pol = POLICIES[policy] if isinstance(policy, str) else int(policy)
+    bi = _abi.BatchIn(R, T, N, pol, N if mips.dim() == 2 else 0, 0,
+                      _ptr(arrive), _ptr(trace["req"]), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
+                      _ptr(trace["init"]), None, None, None,
+                      _ptr(trace.get("region")) if pol == _abi.FOGNET_POLICY_EXT_HIER else None)
+    bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick), _ptr(out.stats))
+    vec = _abi.SignalVectors(cap, _ptr(b["offset"]), _ptr(b["time"]), _ptr(b["value"]), _ptr(b["task"]))
+    ctx.check(ctx._lib.fognet_signal_vectors_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(uo), U,
+                                                 U if uu.dim() == 2 else 0, _ptr(uu), _ptr(ud), r0, Rv, C.byref(vec),
+                                                 _ptr(b["n_unassigned"]), _stream_ptr(dev)), "signal_vectors")
+    if not to_host:
+        return {k: b[k] for k in shapes}
+    got = {k: b[k].cpu().numpy() for k in shapes}
+    if not allow_unassigned and rows > 0:
+        bad = int(got["n_unassigned"].sum())
+        if bad:
+            raise FognetError(_abi.FOGNET_ERR_ARG, f"signal_vectors: {bad} decided publishes name a user outside "
+                                                   f"[0, {U}) (allow_unassigned=True leaves them out)")
+    return got
+
+
 def reduce_user_stats(ctx: Context, user_stats: torch.Tensor, stats: torch.Tensor, R: int, U: int,
                       out: torch.Tensor | None = None) -> np.ndarray:
     """Exact job reduction of user records on the device (fognet_reduce_user_stats_dev):

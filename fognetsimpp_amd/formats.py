@@ -145,6 +145,28 @@ def write_vec(path: str, arrive, dl, node, status, start, node_id=None, run_id: 
                                         _p(s), _p(st), _p(nid)), "write_vec")
 
 
+def write_vec_users(path: str, offset, time, value, U: int, id_base: int = 0, user_module=None, append: bool = False,
+                    run_id: str = "General-0-fognet", network: str = "FogNet") -> None:
+    """The user-side vectors of ONE replication as an OMNeT++ `.vec` (fognet_write_vec_users):
+    ``offset`` is the replication's offset row from the `delay` vector on (``row[N:]``, 3U + 2
+    entries), ``time`` / ``value`` its rows (engine.signal_vectors, copied to the host).
+    ``append``: add the vectors to the file :func:`write_vec` wrote (``id_base`` = N + 1)."""
+    off = np.ascontiguousarray(offset, dtype=np.int64).reshape(-1)
+    t = np.ascontiguousarray(time, dtype=np.int64).reshape(-1)
+    v = np.ascontiguousarray(value, dtype=np.int64).reshape(-1)
+    if U < 0 or off.size != 3 * U + 2 or t.size != v.size or (off.size and int(off.max()) > t.size):
+        raise FognetError(_abi.FOGNET_ERR_ARG, "write_vec_users: offset must hold 3U + 2 entries within time / value")
+    names = None
+    if user_module is not None:
+        mods = [str(m).encode() for m in user_module]
+        if len(mods) != U:
+            raise FognetError(_abi.FOGNET_ERR_ARG, "write_vec_users: user_module length differs from U")
+        names = (C.c_char_p * len(mods))(*mods)
+    _check(_abi.load().fognet_write_vec_users(path.encode(), run_id.encode(), network.encode(), U, id_base, _p(off),
+                                              _p(t), _p(v), C.cast(names, C.c_void_p) if names is not None else None,
+                                              1 if append else 0), "write_vec_users")
+
+
 def gen_trace_mqtt(seed: int, start, interval, uplink, downlink, stop: int, req_base: int = 200, req_span: int = 701,
                    cap: int | None = None) -> dict:
     """Reference task source (fognet_gen_trace_mqtt): per-user tick arrays

@@ -345,6 +345,10 @@ typedef struct fognet_batch_out {
  *     [U]) and n_unassigned [R] likewise: 8-B alignment (user_of: 4 B), nothing outside
  *     [R][U] / [U] / [R] touched, no initialisation needed; a failed replication's row is U
  *     empty records and its n_unassigned is 0.
+ *   The signal vectors (fognet_signal_vectors_dev's offset [Rv][V + 1], time / value / task
+ *     [Rv][cap], n_unassigned [Rv]) likewise: 8-B alignment (task: 4 B), nothing outside them
+ *     touched, no initialisation needed; rows at and past offset[V] keep what they held; a
+ *     failed replication's offsets are all 0 and none of its rows is written.
  *   escalated likewise: 1-B alignment, nothing outside [R][T] touched, no initialisation
  *     needed; a failed replication's row is undefined, like its other per-task rows. */
 
@@ -634,6 +638,72 @@ int fognet_reduce_user_stats_dev(fognet_ctx *ctx, const fognet_user_stats *user_
  * field (ranks combine their [U] records after an all-gather). */
 void fognet_user_stats_init(fognet_user_stats *s);
 void fognet_user_stats_merge(fognet_user_stats *acc, const fognet_user_stats *other);
+
+/* Signal vectors.  The reference records its five signals with `record=stats, vector`; the
+ * vector half lists every emission with its time, in the order the module made them.  One
+ * replication has V = N + 1 + 3U vectors, in this order: the N nodes' queueTime, the broker's
+ * delay, U x latency, U x latencyH1, U x taskTime.  Its rows are the emissions that
+ * fognet_node_stats_dev and fognet_per_user_stats_dev count: over the replication's first
+ * stats[r].n_tasks publishes, with the same emission rule; an emission that overflows the
+ * simtime_t range is no row (the records count it in `overflow`), and a publish whose user_of
+ * lies outside [0, U) gives no user-side row and no delay row (n_unassigned counts them).
+ * Time, value and order of the rows (k the task's node, u its user, the links as above):
+ *   queueTime, node k   time start_tick, value the raw queueTime; in task order (the server is
+ *                       FIFO, so the times are nondecreasing).
+ *   delay, broker       time arrive_tick, value user_ul[u]; in task order.
+ *   latencyH1 / latency / taskTime, user u   value the raw (time - created) * 1000, the time
+ *                       arrive + dl_u for the broker's own pubAck (latencyH1), arrive + dl_k +
+ *                       ul_k + dl_u for the node's first ack (status 5: latency, 4: latencyH1),
+ *                       done + ul_k + dl_u for the completion ack (taskTime); ascending by
+ *     1. the time;
+ *     2. the broker's own pubAck before any relayed ack (publishes precede dynamic events at
+ *        the broker's tick);
+ *     3. among relayed acks, the tick at which the node sent it (time - dl_u - ul_k);
+ *     4. the tick at which the sending event was inserted: arrive_tick[i] for the first ack
+ *        (the task's arrival event, created at the decision), start_tick[i] for the completion
+ *        ack (the RELEASERESOURCE timer, armed at the service start);
+ *     5. a first ack before a completion ack;
+ *     6. the task index.
+ * This is the FES order of the reference; tests/test_signal_vectors.py holds it to every
+ * relayed ack of the reference's own recorded runs.  The key is total (rows equal in all of it
+ * are equal in every column), so the output does not depend on how rows were placed before
+ * ordering.
+ * The CSR of one replication: offset [V + 1] (offset[0] = 0; vector v's rows are
+ * [offset[v], offset[v + 1])), and per row its time (ticks), its raw value (the units of the
+ * records: fognet_moments) and the index of the task that caused it. */
+typedef struct fognet_signal_vectors {
+    int64_t cap;      /* rows per replication in time / value / task: at least 6 * T (one queueTime,
+                         one delay, one latency, two latencyH1 and one taskTime per task at most)  */
+    int64_t *offset;  /* [Rv][V + 1]                                                            */
+    int64_t *time;    /* [Rv][cap]                                                              */
+    int64_t *value;   /* [Rv][cap]                                                              */
+    int32_t *task;    /* [Rv][cap]                                                              */
+} fognet_signal_vectors;
+
+/* The signal vectors of replications [r0, r0 + Rv) of a finished replay, ordered, on the device.
+ * in, out, user_of, U, link_stride and the links: as fognet_per_user_stats_dev ([R][T] /
+ * [R|1][U], indexed by the job's replication r); out->start_tick is needed as well.  vec (host
+ * struct of device pointers) and n_unassigned [Rv] (device, nullable) are indexed by r - r0.
+ * Rows at and past offset[V] are not written, and nothing depends on what the buffers held; two
+ * runs are byte-identical.  A failed replication (status other than FOGNET_OK /
+ * FOGNET_REF_ABORTED) gets all-zero offsets and n_unassigned 0; nothing of its rows, its links
+ * or its user_of row is read.  FOGNET_POLICY_REF_V3 and FOGNET_POLICY_EXT_LAT, with or without
+ * down_tick.  Refused: FOGNET_POLICY_EXT_HIER (FOGNET_ERR_UNSUPPORTED, before anything else is
+ * checked and with nothing written: the place of an escalated task's acks in the order is
+ * builder-defined, and no recording pins it); a statistics-only `out` or one without start_tick,
+ * NULL vec or vec arrays, vec->cap < 6 * T, NULL links with U > 0, NULL user_of with T > 0,
+ * U < 0, a link_stride other than 0 or U, r0 < 0, Rv < 0 or r0 + Rv > R (FOGNET_ERR_ARG);
+ * T >= 2^28 or Rv * V >= 2^31 (FOGNET_ERR_UNSUPPORTED).  Uses the context's workspace (4 B per
+ * replication and vector).
+ * FOGNET_VEC_SORT=hbm (environment, testing): every segment above 64 rows is sorted as segments
+ * above 2,048 rows are (in chunks, the sorting network's wider steps over the segment in HBM),
+ * and the row counters live in the caller's offset row and the workspace, as they do above 8,192
+ * vectors; the results are identical.  FOGNET_VEC_STAGES=1 / 2 (timing
+ * only): stop after the count / the place stage; the rows are then unordered or unwritten. */
+int fognet_signal_vectors_dev(fognet_ctx *ctx, const fognet_batch_in *in, const fognet_batch_out *out,
+                              const int32_t *user_of, int32_t U, int32_t link_stride,
+                              const int64_t *user_ul_tick, const int64_t *user_dl_tick, int32_t r0, int32_t Rv,
+                              const fognet_signal_vectors *vec, int64_t *n_unassigned, void *hip_stream);
 
 /* Exact reduction of R per-replication stats (device pointers) into one job
  * record (device pointer).  Replications with status != OK count in n_failed

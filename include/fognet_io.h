@@ -125,6 +125,23 @@ int fognet_write_vec(const char *path, const char *run_id, const char *network, 
                      const int64_t *arrive_tick, const int64_t *dl_tick /* [N] */, const int32_t *node,
                      const uint8_t *status, const int64_t *start_tick, const int32_t *node_id);
 
+/* OMNeT++ .vec vectors of the user-side signals of ONE replication (host copies of
+ * fognet_signal_vectors_dev's CSR, fognet_hip.h "Signal vectors"): `delay:vector` under
+ * <network>.broker.udpApp[0] (value s) and, per module <network>.<user_module[u] or
+ * "user[u]">.udpApp[0] (fognet_write_sca_users' names), `latency:vector`, `latencyH1:vector`
+ * and `taskTime:vector` (value ms), each with fognet_write_vec's three attr lines, columns
+ * "TV", exact decimal times and values raw * 1e-12; rows in the CSR's order.
+ * offset: the replication's offset row FROM THE delay VECTOR ON, &offset[N]: 3U + 2 entries
+ * (delay, U x latency, U x latencyH1, U x taskTime), indexing the replication's time and
+ * value arrays.  Vector ids: id_base for delay, id_base + 1 + 3u + {0, 1, 2} for user u's
+ * latency, latencyH1, taskTime (after fognet_write_vec: id_base = N + 1).  A vector without a
+ * row is declared and has no data line.  append != 0: the vectors are appended to the file
+ * fognet_write_vec wrote, without a second version/run header; otherwise the file is created
+ * with one.  user_module: [U] names, nullable. */
+int fognet_write_vec_users(const char *path, const char *run_id, const char *network, int32_t U, int32_t id_base,
+                           const int64_t *offset, const int64_t *time, const int64_t *value,
+                           const char *const *user_module, int append);
+
 /* The reference task source (mqttApp2.cc:198-409 with the ini keys of
  * simulations/example/wirelessNet.ini:48-52), restated as a small event
  * simulation of U users and the broker's CONNECT handling:
