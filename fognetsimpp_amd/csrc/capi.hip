@@ -770,54 +770,66 @@ int fognet_run_batch(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_out*
   return FOGNET_OK;
 }
 
+// ---------------------------------------------------------------- passes over a finished replay
+// What the four passes share of their entry points; each keeps its own checks, in its own order, between them.
+struct PassSpec {
+  bool need_start;    // the pass reads start_tick as well as node, status and done_tick
+  bool hier_refused;  // EXT_HIER: refused outright; else only without fognet_batch_out.escalated
+  const char* hier_msg;
+};
+#define FOGNET_NEEDS_ESCALATED \
+  "the per-task outputs do not say which tasks were escalated (replay with fognet_batch_out.escalated)"
+
+static int pass_begin(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out, const PassSpec& p,
+                      fognet::ReplayArgs* a) {
+  if (!c || !out) return FOGNET_ERR_ARG;
+  if (in && in->policy == FOGNET_POLICY_EXT_HIER && (p.hier_refused || !out->escalated))
+    return fail(c, FOGNET_ERR_UNSUPPORTED, p.hier_msg);
+  return prepare(c, in, a);
+}
+
+// (a statistics-only out has no per-task outputs)
+static bool has_task_outputs(const fognet::ReplayArgs& a, const fognet_batch_out* out, const PassSpec& p) {
+  return a.T <= 0 || (out->node && out->status && out->done_tick && (!p.need_start || out->start_tick));
+}
+
+// the device, and the replay's outputs as the pass's inputs
+static int pass_bind(fognet_ctx* c, const fognet_batch_out* out, const PassSpec& p, fognet::ReplayArgs* a) {
+  a->out_node = out->node, a->out_status = out->status, a->out_done = out->done_tick, a->out_stats = out->stats;
+  if (p.need_start) a->out_start = out->start_tick;
+  if (!p.hier_refused && a->policy == FOGNET_POLICY_EXT_HIER) a->out_esc = out->escalated;  // (else never read)
+  return set_device(c);
+}
+
 int fognet_user_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out, const int64_t* user_ul,
                           const int64_t* user_dl, int32_t user_per_task, fognet_user_stats* user_stats, void* stream) {
-  if (!c || !out) return FOGNET_ERR_ARG;
-  if (in && in->policy == FOGNET_POLICY_EXT_HIER && !out->escalated)
-    return fail(c, FOGNET_ERR_UNSUPPORTED,
-                "user signals under EXT_HIER: the acks of an escalated task leave its node hier_up_tick later, and "
-                "the per-task outputs do not say which tasks were escalated (replay with fognet_batch_out.escalated)");
+  static const PassSpec spec = {false, false, "user signals under EXT_HIER: the acks of an escalated task leave its "
+                                              "node hier_up_tick later, and " FOGNET_NEEDS_ESCALATED};
   fognet::ReplayArgs a;
-  int rc = prepare(c, in, &a);
+  int rc = pass_begin(c, in, out, spec, &a);
   if (rc) return rc;
   if (user_per_task != 0 && user_per_task != 1) return fail(c, FOGNET_ERR_ARG, "user_per_task must be 0 or 1");
   if (a.R == 0) return FOGNET_OK;
-  if (!user_ul || !user_dl || !user_stats || !out->stats || (a.T > 0 && (!out->node || !out->status || !out->done_tick)))
+  if (!user_ul || !user_dl || !user_stats || !out->stats || !has_task_outputs(a, out, spec))
     return fail(c, FOGNET_ERR_ARG, "null pointer");
-  rc = set_device(c);
-  if (rc) return rc;
-  a.out_node = out->node;
-  a.out_status = out->status;
-  a.out_done = out->done_tick;
-  a.out_stats = out->stats;
-  if (a.policy == FOGNET_POLICY_EXT_HIER) a.out_esc = out->escalated;  // (not read under the other policies)
+  if ((rc = pass_bind(c, out, spec, &a))) return rc;
   hipError_t e = fognet::launch_user_stats(a, user_ul, user_dl, user_per_task, user_stats, (hipStream_t)stream);
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "user stats launch");
 }
 
 int fognet_node_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out,
                           fognet_node_stats* node_stats, void* stream) {
-  if (!c || !out) return FOGNET_ERR_ARG;
-  if (in && in->policy == FOGNET_POLICY_EXT_HIER && !out->escalated)
-    return fail(c, FOGNET_ERR_UNSUPPORTED,
-                "node statistics under EXT_HIER: an escalated task reaches its node hier_up_tick later, and the "
-                "per-task outputs do not say which tasks were escalated (replay with fognet_batch_out.escalated)");
+  static const PassSpec spec = {true, false, "node statistics under EXT_HIER: an escalated task reaches its node "
+                                             "hier_up_tick later, and " FOGNET_NEEDS_ESCALATED};
   fognet::ReplayArgs a;
-  int rc = prepare(c, in, &a);
+  int rc = pass_begin(c, in, out, spec, &a);
   if (rc) return rc;
   if (a.R == 0) return FOGNET_OK;
   if (!out->stats) return fail(c, FOGNET_ERR_ARG, "null stats");
-  if (a.T > 0 && (!out->node || !out->status || !out->start_tick || !out->done_tick))
+  if (!has_task_outputs(a, out, spec))
     return fail(c, FOGNET_ERR_ARG, "node statistics need the per-task outputs (a statistics-only out has none)");
   if (!node_stats) return fail(c, FOGNET_ERR_ARG, "null node_stats");
-  rc = set_device(c);
-  if (rc) return rc;
-  a.out_node = out->node;
-  a.out_status = out->status;
-  a.out_start = out->start_tick;
-  a.out_done = out->done_tick;
-  a.out_stats = out->stats;
-  if (a.policy == FOGNET_POLICY_EXT_HIER) a.out_esc = out->escalated;  // (not read under the other policies)
+  if ((rc = pass_bind(c, out, spec, &a))) return rc;
   // FOGNET_NODE_STATS=hbm: the accumulators are the caller's records for every N (the layout of
   // N > node_stats_lds_max()), so small tests run both layouts on the same traces
   const hipError_t e = fognet::launch_node_stats(a, node_stats, env_is("FOGNET_NODE_STATS", "hbm"), (hipStream_t)stream);
@@ -839,55 +851,46 @@ int fognet_reduce_node_stats_dev(fognet_ctx* c, const fognet_node_stats* node_st
 int fognet_per_user_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out,
                               const int32_t* user_of, int32_t U, int32_t link_stride, const int64_t* user_ul,
                               const int64_t* user_dl, fognet_user_stats* per_user, int64_t* n_unassigned, void* stream) {
-  if (!c || !out) return FOGNET_ERR_ARG;
-  if (in && in->policy == FOGNET_POLICY_EXT_HIER && !out->escalated)
-    return fail(c, FOGNET_ERR_UNSUPPORTED,
-                "per-user signals under EXT_HIER: the acks of an escalated task leave its node hier_up_tick later, "
-                "and the per-task outputs do not say which tasks were escalated (replay with "
-                "fognet_batch_out.escalated)");
+  static const PassSpec spec = {false, false, "per-user signals under EXT_HIER: the acks of an escalated task leave "
+                                              "its node hier_up_tick later, and " FOGNET_NEEDS_ESCALATED};
   fognet::ReplayArgs a;
-  int rc = prepare(c, in, &a);
+  int rc = pass_begin(c, in, out, spec, &a);
   if (rc) return rc;
   if (U < 0) return fail(c, FOGNET_ERR_ARG, "negative U");
   if (link_stride != 0 && link_stride != U) return fail(c, FOGNET_ERR_ARG, "link_stride must be 0 or U");
   if (a.R == 0) return FOGNET_OK;
   if (!out->stats) return fail(c, FOGNET_ERR_ARG, "null stats");
-  if (a.T > 0 && (!out->node || !out->status || !out->done_tick))
+  if (!has_task_outputs(a, out, spec))
     return fail(c, FOGNET_ERR_ARG, "per-user signals need the per-task outputs (a statistics-only out has none)");
   if (a.T > 0 && !user_of && (U > 0 || n_unassigned)) return fail(c, FOGNET_ERR_ARG, "null user_of");
   if (U > 0 && (!per_user || !user_ul || !user_dl)) return fail(c, FOGNET_ERR_ARG, "null per_user or user links");
-  rc = set_device(c);
-  if (rc) return rc;
-  a.out_node = out->node;
-  a.out_status = out->status;
-  a.out_done = out->done_tick;
-  a.out_stats = out->stats;
-  if (a.policy == FOGNET_POLICY_EXT_HIER) a.out_esc = out->escalated;  // (not read under the other policies)
+  if ((rc = pass_bind(c, out, spec, &a))) return rc;
   // FOGNET_USER_STATS=hbm: the accumulators are the caller's records for every U (the layout of
   // U > per_user_stats_lds_max()), so small tests run both layouts on the same traces
-  const hipError_t e = fognet::launch_per_user_stats(a, user_of, U, link_stride, user_ul, user_dl, per_user, n_unassigned,
-                                                     env_is("FOGNET_USER_STATS", "hbm"), (hipStream_t)stream);
+  const fognet::UserLinks users{user_of, user_ul, user_dl, U, link_stride};
+  const hipError_t e = fognet::launch_per_user_stats(a, users, per_user, n_unassigned, env_is("FOGNET_USER_STATS", "hbm"),
+                                                     (hipStream_t)stream);
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "per-user stats launch");
 }
+
+#undef FOGNET_NEEDS_ESCALATED
 
 int fognet_signal_vectors_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out,
                               const int32_t* user_of, int32_t U, int32_t link_stride, const int64_t* user_ul,
                               const int64_t* user_dl, int32_t r0, int32_t Rv, const fognet_signal_vectors* vec,
                               int64_t* n_unassigned, void* stream) {
-  if (!c || !out) return FOGNET_ERR_ARG;
-  if (in && in->policy == FOGNET_POLICY_EXT_HIER)
-    return fail(c, FOGNET_ERR_UNSUPPORTED,
-                "signal vectors under EXT_HIER: where an escalated task's acks stand among the acks of their tick is "
-                "builder-defined, and no recording of the reference pins it");
+  static const PassSpec spec = {true, true, "signal vectors under EXT_HIER: where an escalated task's acks stand among "
+                                            "the acks of their tick is builder-defined, and no recording of the "
+                                            "reference pins it"};
   fognet::ReplayArgs a;
-  int rc = prepare(c, in, &a);
+  int rc = pass_begin(c, in, out, spec, &a);
   if (rc) return rc;
   if (U < 0) return fail(c, FOGNET_ERR_ARG, "negative U");
   if (link_stride != 0 && link_stride != U) return fail(c, FOGNET_ERR_ARG, "link_stride must be 0 or U");
   if (r0 < 0 || Rv < 0 || (int64_t)r0 + Rv > a.R) return fail(c, FOGNET_ERR_ARG, "[r0, r0 + Rv) must lie in [0, R)");
   if (Rv == 0) return FOGNET_OK;
   if (!out->stats) return fail(c, FOGNET_ERR_ARG, "null stats");
-  if (a.T > 0 && (!out->node || !out->status || !out->start_tick || !out->done_tick))
+  if (!has_task_outputs(a, out, spec))
     return fail(c, FOGNET_ERR_ARG, "signal vectors need the per-task outputs, start_tick included");
   if (a.T > 0 && !user_of) return fail(c, FOGNET_ERR_ARG, "null user_of");
   if (U > 0 && (!user_ul || !user_dl)) return fail(c, FOGNET_ERR_ARG, "null user links");
@@ -897,8 +900,7 @@ int fognet_signal_vectors_dev(fognet_ctx* c, const fognet_batch_in* in, const fo
   const int64_t V = (int64_t)a.N + 1 + 3 * (int64_t)U;
   if (a.T >= (1 << 28) || V * Rv >= ((int64_t)1 << 31))
     return fail(c, FOGNET_ERR_UNSUPPORTED, "signal vectors: T >= 2^28 or Rv * V >= 2^31");
-  rc = set_device(c);
-  if (rc) return rc;
+  if ((rc = pass_bind(c, out, spec, &a))) return rc;
   fognet::VecWs w{};
   fognet::WsCursor measure{nullptr};
   rc = ensure(c, (void**)&c->ring, &c->ring_bytes, fognet::signal_vectors_ws(w, (size_t)Rv, (size_t)V, measure),
@@ -906,18 +908,13 @@ int fognet_signal_vectors_dev(fognet_ctx* c, const fognet_batch_in* in, const fo
   if (rc) return rc;
   fognet::WsCursor carve{reinterpret_cast<unsigned char*>(c->ring)};
   (void)fognet::signal_vectors_ws(w, (size_t)Rv, (size_t)V, carve);
-  a.out_node = out->node;
-  a.out_status = out->status;
-  a.out_start = out->start_tick;
-  a.out_done = out->done_tick;
-  a.out_stats = out->stats;
   // FOGNET_VEC_SORT=hbm: every segment is sorted in HBM and the counters live in HBM (the layouts of
   // large segments and of V > signal_vectors_lds_max()), so small tests run both on the same traces.
   // FOGNET_VEC_STAGES=1 / 2: stop after the count / place stage (tools/time_signal_vectors.py).
   const int stages = env_is("FOGNET_VEC_STAGES", "1") ? 1 : env_is("FOGNET_VEC_STAGES", "2") ? 2 : 3;
-  const hipError_t e = fognet::launch_signal_vectors(a, user_of, U, link_stride, user_ul, user_dl, r0, Rv, *vec,
-                                                     n_unassigned, w.cursor, env_is("FOGNET_VEC_SORT", "hbm"), stages,
-                                                     (hipStream_t)stream);
+  const fognet::UserLinks users{user_of, user_ul, user_dl, U, link_stride};
+  const hipError_t e = fognet::launch_signal_vectors(a, users, r0, Rv, *vec, n_unassigned, w.cursor,
+                                                     env_is("FOGNET_VEC_SORT", "hbm"), stages, (hipStream_t)stream);
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "signal vectors launch");
 }
 

@@ -433,9 +433,14 @@ hipError_t launch_reduce_node_stats(const fognet_node_stats* in, const fognet_re
 // Per-user signals of a finished replay and their job reduction (per_user_stats.hip).  Up to
 // per_user_stats_lds_max() users the accumulators and the user links live in LDS unless force_hbm;
 // the reduction is one workgroup per user over any R and needs no workspace.
+struct UserLinks {
+  const int32_t* user_of;  // [R][T] the user of every publish
+  const int64_t* ul;       // [R|1][U] user -> broker
+  const int64_t* dl;       // [R|1][U] broker -> user
+  int32_t U, link_stride;
+};
 int32_t per_user_stats_lds_max();
-hipError_t launch_per_user_stats(const ReplayArgs& a, const int32_t* user_of, int32_t U, int32_t link_stride,
-                                 const int64_t* user_ul, const int64_t* user_dl, fognet_user_stats* out,
+hipError_t launch_per_user_stats(const ReplayArgs& a, const UserLinks& users, fognet_user_stats* out,
                                  int64_t* n_unassigned, bool force_hbm, hipStream_t s);
 hipError_t launch_reduce_user_stats(const fognet_user_stats* in, const fognet_rep_stats* stats, int32_t R, int32_t U,
                                     fognet_user_stats* out, hipStream_t s);
@@ -445,8 +450,7 @@ hipError_t launch_reduce_user_stats(const fognet_user_stats* in, const fognet_re
 // [Rv][V] cursors (VecWs).  stages: 1 stops after count, 2 after place (timing), 3: the whole pass.
 int32_t signal_vectors_lds_max();
 int32_t signal_vectors_sort_lds_max();
-hipError_t launch_signal_vectors(const ReplayArgs& a, const int32_t* user_of, int32_t U, int32_t link_stride,
-                                 const int64_t* user_ul, const int64_t* user_dl, int32_t r0, int32_t Rv,
+hipError_t launch_signal_vectors(const ReplayArgs& a, const UserLinks& users, int32_t r0, int32_t Rv,
                                  const fognet_signal_vectors& vec, int64_t* n_unassigned, uint32_t* cursor,
                                  bool force_hbm, int stages, hipStream_t s);
 // v2 model replay (replay_v2.hip)

@@ -2,8 +2,8 @@
 // (fognet_signal_vectors_dev): what the reference records with `vector` per fog node
 // (queueTime, ComputeBrokerApp3.ned:45-46), at the broker (delay, BrokerBaseApp3.ned:32-33)
 // and per user module (latency, latencyH1, taskTime, mqttApp2.ned:49-54).  The rows are the
-// emissions node_stats.hip and per_user_stats.hip count, with the same emission rule; their
-// order is the one fognet_hip.h states ("Signal vectors").
+// emissions node_stats.hip and per_user_stats.hip count: all three take them from signals.h's
+// emission rule.  Their order is the one fognet_hip.h states ("Signal vectors").
 //
 // One CSR per replication over V = N + 1 + 3U vectors, in three kernels on the caller's stream:
 //   count  one 256-thread workgroup per replication streams the per-task rows (33 B per task,
@@ -30,25 +30,20 @@
 // act as +infinity without being stored or touched, and any segment length sorts in place.
 // The key is total apart from rows equal in every word, so the result does not depend on where
 // the cursors put the rows.
-#include "replay_common.h"
+#include "signals.h"
 
 namespace fognet {
 
 namespace {
 
-constexpr int kVecThreads = 256;
-constexpr int kVecWaves = kVecThreads / kWave;
+constexpr int kVecThreads = kPassThreads;
 constexpr int kVecLdsMax = 8192;       // one 32-bit count or cursor per vector: 32 KiB of LDS
 constexpr int kVecSortThreads = 1024;  // one compare-exchange per thread and step at kVecSortLdsMax rows
 constexpr int kVecSortLdsMax = 2048;   // 20 B per row (time, value, task): 40 KiB of the 64 KiB a workgroup may take
 constexpr int kVecSortForcedChunk = 64; // FOGNET_VEC_SORT=hbm: small segments take the HBM steps as well
 constexpr uint32_t kRelayedBit = 0x80000000u;
 
-struct VecArgs {
-  const int32_t* user_of;  // [R][T]
-  const int64_t* ul;       // [R|1][U] user -> broker
-  const int64_t* dl;       // [R|1][U] broker -> user
-  int32_t U, link_stride;
+struct VecArgs : UserLinks {
   int32_t r0, Rv, V;
   int64_t cap;             // rows per replication in time / value / task
   int64_t* offset;         // [Rv][V + 1]
@@ -60,74 +55,31 @@ struct VecArgs {
   int32_t sort_chunk;      // rows of a segment sorted together in LDS (a power of two, <= kVecSortLdsMax)
 };
 
-struct VecRow {
-  int64_t t, start, done;
-  int32_t node, user;
-  uint32_t status;
-};
-
-__device__ __forceinline__ VecRow load_row(const ReplayArgs& A, const int32_t* user_of, size_t o) {
-  return VecRow{A.arrive[o], A.out_start[o], A.out_done[o], A.out_node[o], user_of[o], (uint32_t)A.out_status[o]};
-}
-
-// The emissions of one decided publish: f(vector, time, value, relayed-ack mark).
+// The rows of one decided publish, signals.h's emissions with a value in the simtime_t range:
+// f(vector, time, value, relayed-ack mark).  A publish of no known user has its queueTime row alone.
 template <class F>
 __device__ __forceinline__ void for_each_emission(const ReplayArgs& A, const VecArgs& P, size_t nbase, size_t lbase,
-                                                  const VecRow& x, F&& f) {
+                                                  const Row& x, F&& f) {
   const int N = A.N, U = P.U;
-  const bool node_ok = (uint32_t)x.node < (uint32_t)N;
-  // (a decided publish's node lies in [0, N); an index outside it emits no queueTime and reads node 0's links)
-  const size_t k = nbase + (size_t)(node_ok ? x.node : 0);
-  if (node_ok && x.status == 4u && x.start >= 0) {  // queueTime (ComputeBrokerApp3.cc:238), at the service start
-    int64_t raw;
-    if (qtime_raw(x.start, x.t + A.dl[k], raw)) f(x.node, x.start, raw, 0u);
-  }
   const uint32_t u = (uint32_t)x.user;
-  if (u >= (uint32_t)U) return;
-  const int64_t uu = P.ul[lbase + u], ud = P.dl[lbase + u];
-  const int64_t created = x.t - uu;
-  f(N, x.t, uu, 0u);  // delay: at the broker (BrokerBaseApp3.cc:143), a simtime_t (s)
-  const int v_lat = N + 1 + (int)u, v_h1 = v_lat + U, v_tt = v_h1 + U;
+  const bool known = u < (uint32_t)U;
+  const Emissions e = emissions(
+      A, x, [&](int k) { return A.dl[nbase + k]; }, [&](int k) { return A.ul[nbase + k]; },
+      known ? P.ul[lbase + u] : 0, known ? P.dl[lbase + u] : 0);
   int64_t raw;
-  if (ms_raw(x.t + ud - created, raw)) f(v_h1, x.t + ud, raw, 0u);  // the broker's own pubAck, status 4
-  const int64_t relay = A.ul[k] + ud;                               // node -> broker -> user
-  const int64_t first = x.t + A.dl[k] + relay;                      // the node's ack, sent at the task's arrival
-  if (x.status == 5u) {
-    if (ms_raw(first - created, raw)) f(v_lat, first, raw, 0u);  // "task assigned" -> latency
-  } else if (x.status == 4u) {
-    if (ms_raw(first - created, raw)) f(v_h1, first, raw, kRelayedBit);  // "task queued" -> latencyH1
-  }
-  // (status 9: the task reached a crashed node, which sends no ack)
-  if (x.done >= 0 && ms_raw(x.done + relay - created, raw)) f(v_tt, x.done + relay, raw, 0u);  // status 6 -> taskTime
+  if (e.queued && qtime_raw(e.queue_start, e.queue_enq, raw)) f(x.node, e.queue_start, raw, 0u);
+  if (!known) return;
+  f(N, x.t, e.delay, 0u);
+  const int v_lat = N + 1 + (int)u, v_h1 = v_lat + U, v_tt = v_h1 + U;
+  if (ms_raw(e.puback_d, raw)) f(v_h1, e.puback_at, raw, 0u);
+  if (e.first != kAckNone && ms_raw(e.first_d, raw))
+    f(e.first == kAckLatency ? v_lat : v_h1, e.first_at, raw, e.first == kAckLatency ? 0u : kRelayedBit);
+  if (e.completed && ms_raw(e.done_d, raw)) f(v_tt, e.done_at, raw, 0u);
 }
 
-// One workgroup streams replication r's first n decided publishes (per_user_stats.hip's loop):
-// lanes past n reload the chunk's first task (in bounds, unused).
-template <class F>
-__device__ __forceinline__ void stream_rows(const ReplayArgs& A, const VecArgs& P, int r, int n, F&& f) {
-  const int lane = (int)threadIdx.x & (kWave - 1), wave = (int)threadIdx.x / kWave;
-  const size_t tbase = (size_t)r * (size_t)A.T;
-  const int chunks = (n + kWave - 1) / kWave;
-  auto offset_of = [&](int c) { return tbase + (size_t)(c * kWave + lane < n ? c * kWave + lane : c * kWave); };
-  VecRow cur{};
-  if (wave < chunks) cur = load_row(A, P.user_of, offset_of(wave));
-  for (int c = wave; c < chunks; c += kVecWaves) {
-    VecRow nxt = cur;  // the next chunk's loads are in flight while this one is handled
-    if (c + kVecWaves < chunks) nxt = load_row(A, P.user_of, offset_of(c + kVecWaves));
-    const int i = c * kWave + lane;
-    f(cur, i, i < n);
-    cur = nxt;
-  }
-}
-
-__device__ __forceinline__ int decided_tasks(const ReplayArgs& A, int r) {
-  const int64_t n64 = A.out_stats[r].n_tasks;  // decided tasks (written by the replay)
-  return (int)(n64 < 0 ? 0 : n64 > A.T ? A.T : n64);
-}
-
-__device__ __forceinline__ bool rep_ok(const ReplayArgs& A, int r) {
-  const int32_t s = A.out_stats[r].status;
-  return s == FOGNET_OK || s == FOGNET_REF_ABORTED;
+// the per-task columns of the count and place kernels (33 B per task; never the escalation flags)
+__device__ __forceinline__ Row load_vec_row(const ReplayArgs& A, const VecArgs& P, size_t o) {
+  return load_row<kColStart | kColUser>(A, P.user_of, o);
 }
 
 // a count the workgroup's atomics left in the caller's row (read where the atomics were performed)
@@ -159,7 +111,8 @@ __global__ __launch_bounds__(kVecThreads) void vec_count_kernel(ReplayArgs A, Ve
   __syncthreads();
   const size_t nbase = (size_t)r * (size_t)A.node_stride, lbase = (size_t)r * (size_t)P.link_stride;
   uint32_t unassigned = 0u;  // per wavefront (uniform)
-  stream_rows(A, P, r, decided_tasks(A, r), [&](const VecRow& x, int, bool decided) {
+  auto load = [&](size_t o) { return load_vec_row(A, P, o); };
+  stream_rows(A, r, decided_tasks(A, r), load, [&](const Row& x, int, bool decided) {
     unassigned += (uint32_t)__popcll(ballot(decided && (uint32_t)x.user >= (uint32_t)P.U));
     if (!decided) return;
     for_each_emission(A, P, nbase, lbase, x, [&](int v, int64_t, int64_t, uint32_t) {
@@ -212,7 +165,8 @@ __global__ __launch_bounds__(kVecThreads) void vec_place_kernel(ReplayArgs A, Ve
   // Every decided publish of a known user emits one delay row, and the vector is in task order: where no
   // publish is unassigned, row i is task i's and needs neither a cursor nor the order stage.
   const bool delay_dense = off[A.N + 1] - off[A.N] == (int64_t)n;
-  stream_rows(A, P, r, n, [&](const VecRow& x, int i, bool decided) {
+  auto load = [&](size_t o) { return load_vec_row(A, P, o); };
+  stream_rows(A, r, n, load, [&](const Row& x, int i, bool decided) {
     if (!decided) return;
     for_each_emission(A, P, nbase, lbase, x, [&](int v, int64_t time, int64_t value, uint32_t mark) {
       const int64_t slot = off[v] + (v == A.N && delay_dense ? (int64_t)i : (int64_t)atomicAdd(&cur[v], 1u));
@@ -253,7 +207,7 @@ __device__ __forceinline__ void tie_words(const SortCtx& c, uint32_t task, int64
   } else {  // the node's first ack: sent at the task's arrival, an event created at the decision
     const int32_t k = A.out_node[o];
     const int64_t t = A.arrive[o];
-    sent = t + A.dl[c.nbase + (size_t)((uint32_t)k < (uint32_t)A.N ? k : 0)];
+    sent = t + A.dl[c.nbase + (size_t)link_node(A, k)];
     inserted = t;
   }
 }
@@ -364,14 +318,13 @@ __global__ __launch_bounds__(kVecSortThreads) void vec_sort_kernel(ReplayArgs A,
 int32_t signal_vectors_lds_max() { return kVecLdsMax; }
 int32_t signal_vectors_sort_lds_max() { return kVecSortLdsMax; }
 
-hipError_t launch_signal_vectors(const ReplayArgs& a, const int32_t* user_of, int32_t U, int32_t link_stride,
-                                 const int64_t* user_ul, const int64_t* user_dl, int32_t r0, int32_t Rv,
+hipError_t launch_signal_vectors(const ReplayArgs& a, const UserLinks& users, int32_t r0, int32_t Rv,
                                  const fognet_signal_vectors& vec, int64_t* n_unassigned, uint32_t* cursor,
                                  bool force_hbm, int stages, hipStream_t s) {
   if (Rv <= 0) return hipSuccess;
-  const int32_t V = a.N + 1 + 3 * U;
-  const VecArgs p{user_of, user_ul, user_dl, U, link_stride, r0, Rv, V, vec.cap, vec.offset, vec.time, vec.value,
-                  vec.task, n_unassigned, cursor, force_hbm ? kVecSortForcedChunk : kVecSortLdsMax};
+  const int32_t V = a.N + 1 + 3 * users.U;
+  const VecArgs p{users, r0, Rv, V, vec.cap, vec.offset, vec.time, vec.value, vec.task, n_unassigned, cursor,
+                  force_hbm ? kVecSortForcedChunk : kVecSortLdsMax};
   const bool lds = V <= kVecLdsMax && !force_hbm;
   const size_t lds_bytes = lds ? (size_t)V * sizeof(uint32_t) : 0;
   if (lds)

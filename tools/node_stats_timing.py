@@ -13,6 +13,8 @@ escalates, and its saturating recipe, T = 32,768, where every replication does):
 without and with the per-task escalation flags (fognet_batch_out.escalated, one more byte
 per task), then the user-signal and per-node passes that read them (34 B per task).
 
+FOGNET_LIB=build/live/<name>/libfognet_hip.so times a variant build (tools/build_variant.sh).
+
   python tools/node_stats_timing.py [--out profiles/node_stats_timing.txt] [--reps N] [--shapes c3,c5flat]
 """
 from __future__ import annotations
@@ -26,8 +28,11 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import fognetsimpp_amd as fa  # noqa: E402
 from fognetsimpp_amd import _abi  # noqa: E402
+
+if os.environ.get("FOGNET_LIB"):  # a variant build (tools/build_variant.sh)
+    _abi.LIB_PATH = os.environ["FOGNET_LIB"]
+import fognetsimpp_amd as fa  # noqa: E402
 
 SHAPES = {"c3": (4096, 100_000, 256), "c5flat": (1024, 10_000, 10_000),
           "c5hier": (1024, 10_000, 10_000), "c5sat": (1024, 32_768, 10_000)}
@@ -93,7 +98,8 @@ def main() -> int:
     args = ap.parse_args()
     ctx = fa.Context(0)
     dev = torch.device("cuda", 0)
-    lines = [f"device: {torch.cuda.get_device_name(0)}; median of {args.reps} timed launches after {args.warmup} warm-up"]
+    lines = [f"device: {torch.cuda.get_device_name(0)}; library {os.path.relpath(_abi.LIB_PATH)}; median of {args.reps} "
+             f"timed launches after {args.warmup} warm-up"]
     for name in args.shapes.split(","):
         R, T, N = SHAPES[name]
         if name in ("c5hier", "c5sat"):
