@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CXXFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
 SRC_DIR := fognetsimpp_amd/csrc
-SRCS := $(SRC_DIR)/capi.hip $(SRC_DIR)/replay.hip $(SRC_DIR)/replay_wide.hip $(SRC_DIR)/replay_v2.hip $(SRC_DIR)/replay_region.hip $(SRC_DIR)/decide.hip $(SRC_DIR)/tracegen.hip $(SRC_DIR)/user_stats.hip $(SRC_DIR)/node_stats.hip $(SRC_DIR)/per_user_stats.hip $(SRC_DIR)/signal_vectors.hip
+SRCS := $(SRC_DIR)/capi.hip $(SRC_DIR)/replay.hip $(SRC_DIR)/replay_wide.hip $(SRC_DIR)/replay_v2.hip $(SRC_DIR)/replay_region.hip $(SRC_DIR)/decide.hip $(SRC_DIR)/tracegen.hip $(SRC_DIR)/user_stats.hip $(SRC_DIR)/node_stats.hip $(SRC_DIR)/per_user_stats.hip $(SRC_DIR)/signal_vectors.hip $(SRC_DIR)/replay_assigned.hip
 HDRS := include/fognet_hip.h include/fognet_io.h $(SRC_DIR)/internal.h $(SRC_DIR)/workspace.h $(SRC_DIR)/replay_common.h $(SRC_DIR)/signals.h
 OBJDIR := build/obj
 OBJS := $(patsubst $(SRC_DIR)/%.hip,$(OBJDIR)/%.o,$(SRCS)) $(OBJDIR)/io.o
@@ -95,6 +95,11 @@ asan:
 	! ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/fognet_replay -f tests/scenarios/fog5.ini -c Early --users 'user[2]' --dry-run 2> $(ASAN_DIR)/err.txt
 	grep -q "divide by the unadvertised MIPS 0" $(ASAN_DIR)/err.txt
 	! ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/fognet_replay -f tests/scenarios/fog5.ini --users 'user[2]' --ring 1000 --dry-run 2> $(ASAN_DIR)/err.txt
+	ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/fognet_replay -f tests/scenarios/fog5.ini --users 'user[4]' --reps 2 \
+	  --assign random:7 --dry-run > /dev/null
+	! ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/fognet_replay -f tests/scenarios/fog5.ini --users 'user[2]' --assign rr \
+	  --policy EXT_LAT --dry-run 2> $(ASAN_DIR)/err.txt
+	grep -q "not together with --policy" $(ASAN_DIR)/err.txt
 	@echo "asan: oracle, io and driver clean"
 
 .PHONY: asan

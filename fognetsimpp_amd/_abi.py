@@ -39,6 +39,8 @@ ABI_VERSION = 10
 HIST_METRICS = 2  # 0 queueTime, 1 response
 HIST_BINS = 64
 COMM_ID_BYTES = 128  # FOGNET_COMM_ID_BYTES
+ASSIGNED_TILE = 64  # FOGNET_ASSIGNED_TILE: tasks per tile of the assigned replay
+ASSIGNED_LDS_NODES = 1024  # FOGNET_ASSIGNED_LDS_NODES: nodes whose carries the assigned replay keeps in LDS
 
 
 class RepStats(C.Structure):
@@ -206,6 +208,8 @@ SIGNATURES = {
     "fognet_run_batch": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut)]),
     "fognet_replay_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P]),
     "fognet_rep_stats_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P]),
+    "fognet_replay_assigned_dev": (C.c_int, [P, C.POINTER(BatchIn), P, C.POINTER(BatchOut), P]),
+    "fognet_run_assigned_dev": (C.c_int, [P, C.POINTER(BatchIn), P, C.POINTER(BatchOut), P]),
     "fognet_user_stats_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P, P, C.c_int32, P, P]),
     "fognet_run_v2_dev": (C.c_int, [P, C.POINTER(V2In), C.POINTER(V2Out), P]),
     "fognet_reduce_stats_dev": (C.c_int, [P, P, C.c_int32, P, P]),

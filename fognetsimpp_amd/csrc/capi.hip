@@ -688,6 +688,71 @@ int fognet_run_batch_dev(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_
   return stage(c, in, out, stream, 3);
 }
 
+// The assigned replay (replay_assigned.hip).  stats: fognet_run_assigned_dev.
+static int run_assigned(fognet_ctx* c, const fognet_batch_in* in, const int32_t* assign, fognet_batch_out* out,
+                        void* stream, bool stats) {
+  if (!c || !out) return FOGNET_ERR_ARG;
+  if (!in) return fail(c, FOGNET_ERR_ARG, "null batch");
+  if (in->N > fognet::kWideBigMaxNodes)
+    return fail(c, FOGNET_ERR_UNSUPPORTED, "assigned replay: N > 1048576 (the limit of every replay here)");
+  // no broker decides: what only a decision reads is not read
+  fognet_batch_in b = *in;
+  b.policy = FOGNET_POLICY_REF_V3;
+  b.ring_capacity = 0;
+  b.region = nullptr;
+  b.hier_up_tick = 0;
+  b.hier_threshold_s = 0;
+  fognet::ReplayArgs a;
+  int rc = prepare(c, &b, &a);
+  if (rc) return rc;
+  if (a.R > 0 && !out->stats) return fail(c, FOGNET_ERR_ARG, "stats output is required (per-replication status)");
+  const bool tasks = a.R > 0 && a.T > 0;
+  if (tasks && (!out->node || !out->status || !out->start_tick || !out->done_tick))
+    return fail(c, FOGNET_ERR_ARG, "assigned replay: all four per-task arrays are required (no statistics-only out)");
+  if (tasks && !assign) return fail(c, FOGNET_ERR_ARG, "assigned replay: null assign");
+  if (stats && out->node_energy_j && !a.p_busy)
+    return fail(c, FOGNET_ERR_ARG, "node_energy_j needs the power model (p_busy_w/p_idle_w)");
+  if (a.R == 0) return FOGNET_OK;
+  if ((rc = set_device(c))) return rc;
+  a.out_node = out->node;
+  a.out_status = out->status;
+  a.out_start = out->start_tick;
+  a.out_done = out->done_tick;
+  a.out_stats = out->stats;
+  if (stats) {
+    a.out_energy = out->node_energy_j;
+    a.hist = out->hist;
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  if (out->escalated && tasks) {  // nobody escalates
+    const hipError_t e = hipMemsetAsync(out->escalated, 0, (size_t)a.R * (size_t)a.T, s);
+    if (e != hipSuccess) return hip_fail(c, e, "escalated clear");
+  }
+  // FOGNET_ASSIGNED=hbm: counts and carries in the workspace for every N (the layout of
+  // N > replay_assigned_lds_max()), so small tests run both layouts on the same traces
+  const bool force_hbm = env_is("FOGNET_ASSIGNED", "hbm");
+  const bool carry_hbm = force_hbm || a.N > fognet::replay_assigned_lds_max();
+  fognet::AssignedWs w;
+  rc = carve(c, "assigned replay workspace", [&](fognet::WsCursor& v) {
+    return fognet::assigned_ws(w, (size_t)a.R, (size_t)a.T, (size_t)a.N, carry_hbm ? (size_t)a.R * (size_t)a.N : 0, v);
+  });
+  if (rc) return rc;
+  // FOGNET_ASSIGNED_STAGES=1 (timing only): stop after the validation + count kernel; nothing is written then
+  const int stages = env_is("FOGNET_ASSIGNED_STAGES", "1") ? 1 : 2;
+  const hipError_t e = fognet::launch_replay_assigned(a, assign, w, stats, force_hbm, stages, s);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "assigned replay launch");
+}
+
+int fognet_replay_assigned_dev(fognet_ctx* c, const fognet_batch_in* in, const int32_t* assign, fognet_batch_out* out,
+                               void* stream) {
+  return run_assigned(c, in, assign, out, stream, false);
+}
+
+int fognet_run_assigned_dev(fognet_ctx* c, const fognet_batch_in* in, const int32_t* assign, fognet_batch_out* out,
+                            void* stream) {
+  return run_assigned(c, in, assign, out, stream, true);
+}
+
 int fognet_run_batch(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_out* out) {
   if (!c || !in || !out) return FOGNET_ERR_ARG;
   fognet::ReplayArgs chk;

@@ -34,6 +34,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <random>
+#include <sstream>
 #include <string>
 #include <chrono>
 #include <thread>
@@ -336,6 +338,8 @@ struct Options {
   int64_t dl = kMs, ul = kMs, user_ul = kMs, user_dl = kMs, stop = kNoTick;
   bool user_dl_set = false, dry_run = false, policy_set = false, quiet = false, show = false, node_stats = false, user_stats = false, vec_users = false;
   int policy = FOGNET_POLICY_REF_V3;
+  int assign = 0;            // --assign: 0 the broker decides, 1 round-robin, 2 random
+  uint64_t assign_seed = 0;  // --assign random:SEED
   double p_busy = -1.0, p_idle = -1.0;
 };
 
@@ -472,6 +476,10 @@ void usage() {
       "  --stop T             override stopTime / sim-time-limit\n"
       "  --reps R --seed S    replications, glibc srand seed of replication 0 (default 1 1)\n"
       "  --policy REF_V3|EXT_LAT   decision policy of a BrokerBaseApp3 run (default REF_V3)\n"
+      "  --assign rr|random[:SEED]   BrokerBaseApp3 runs: no broker decides (fognet_run_assigned_dev); rr sends\n"
+      "                       task i to node i mod N; random draws from std::mt19937_64(SEED + replication)\n"
+      "                       (SEED default 0, replication = its index in the job) and sends task i to\n"
+      "                       the i-th raw draw mod N, in trace order; not with --policy or BrokerBaseApp2\n"
       "  --power BUSY,IDLE    node power model in W (builder-defined energy statistic)\n"
       "  --ring N             per-node pending capacity (power of two)\n"
       "  --trace-out FILE     write the FOGNTRC1 trace  --sca FILE / --vec FILE (replication 0)\n"
@@ -525,6 +533,16 @@ Options parse_args(int argc, char** argv) {
       else if (v == "EXT_LAT") o.policy = FOGNET_POLICY_EXT_LAT;
       else die("--policy: REF_V3 or EXT_LAT");
       o.policy_set = true;
+    } else if (a == "--assign") {
+      const std::string v = need(i);
+      if (v == "rr") o.assign = 1;
+      else if (v == "random") o.assign = 2;
+      else if (v.rfind("random:", 0) == 0) {
+        o.assign = 2;
+        const long long sd = parse_int(v.substr(7), "--assign random:SEED");
+        if (sd < 0) die("--assign random:SEED: SEED must be >= 0");
+        o.assign_seed = (uint64_t)sd;
+      } else die("--assign: rr or random[:SEED]");
     } else if (a == "--power") {
       const std::vector<std::string> p = split(need(i), ',');
       if (p.size() != 2) die("--power BUSY,IDLE");
@@ -555,6 +573,7 @@ Options parse_args(int argc, char** argv) {
   if (o.vec_users && o.vec.empty()) die("--vec-users appends to replication 0's .vec: give --vec FILE");
   if (o.vec_users && !o.trace_in.empty()) die("--vec-users needs the ini's user modules (-f INI): a trace file names no users");
   if (o.vec_users && o.user_dl < 0) die("--vec-users needs a broker->user latency (--user-dl none gives the acks no way back)");
+  if (o.assign && o.policy_set) die("--assign replaces the broker's decision: not together with --policy");
   if (o.world > 1 && o.comm_id.empty()) die("--world > 1 needs --comm-id FILE (the communicator id's rendezvous)");
   if (o.reps < o.world) die("--reps must be >= --world (every rank replays a block of replications)");
   if (o.ring != 0 && (o.ring < 2 || o.ring > (1 << 15) || (o.ring & (o.ring - 1)) != 0))
@@ -784,8 +803,80 @@ void append_user_vectors(const Options& o, fognet_ctx* ctx, const fognet_batch_i
         "vec users");
 }
 
+// --assign: the rule's name for the run attributes and the summary
+std::string assign_name(const Options& o) {
+  return o.assign == 1 ? "rr" : "random:" + std::to_string(o.assign_seed);
+}
+
+// --assign: the decisions [R][T] of the rule (r0: the job's index of this rank's first replication)
+std::vector<int32_t> make_assignment(const Options& o, const fognet_batch_in& in, int r0) {
+  std::vector<int32_t> a((size_t)in.R * (size_t)in.T);
+  const uint64_t N = (uint64_t)std::max(in.N, 1);
+  for (int32_t r = 0; r < in.R; ++r) {
+    std::mt19937_64 gen(o.assign_seed + (uint64_t)(r0 + r));
+    for (int32_t i = 0; i < in.T; ++i)
+      a[(size_t)r * in.T + i] = (int32_t)((o.assign == 1 ? (uint64_t)i : (uint64_t)gen()) % N);
+  }
+  return a;
+}
+
+// --assign: fognet_run_assigned_dev over device copies of the host batch; the outputs come back to `out`
+int run_assigned_host(fognet_ctx* ctx, const fognet_batch_in& in, const std::vector<int32_t>& assign,
+                      const fognet_batch_out& out) {
+  const size_t R = (size_t)in.R, RT = R * (size_t)in.T, N = (size_t)in.N, NRN = (in.node_stride ? R : 1) * N;
+  auto up = [](const auto* h, size_t n) {
+    return dev_copy(std::vector<std::remove_cv_t<std::remove_pointer_t<decltype(h)>>>(h, h + n));
+  };
+  fognet_batch_in din = in;
+  din.arrive_tick = up(in.arrive_tick, RT), din.req_mips = up(in.req_mips, RT), din.mips = up(in.mips, NRN);
+  din.dl_tick = up(in.dl_tick, NRN), din.ul_tick = up(in.ul_tick, NRN), din.init_adv_tick = up(in.init_adv_tick, NRN);
+  if (in.p_busy_w) din.p_busy_w = up(in.p_busy_w, NRN), din.p_idle_w = up(in.p_idle_w, NRN);
+  int32_t* d_assign = dev_copy(assign);
+  fognet_batch_out dout{dev_alloc<int32_t>(RT), dev_alloc<uint8_t>(RT), dev_alloc<int64_t>(RT), dev_alloc<int64_t>(RT),
+                        dev_alloc<fognet_rep_stats>(R), nullptr,
+                        dev_copy(std::vector<int64_t>(out.hist, out.hist + FOGNET_HIST_METRICS * FOGNET_HIST_BINS))};
+  const int rc = fognet_run_assigned_dev(ctx, &din, d_assign, &dout, nullptr);
+  if (rc == FOGNET_OK) {
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    auto down = [](void* h, const void* d, size_t bytes) {
+      if (bytes) hip_check(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    };
+    down(out.node, dout.node, RT * 4), down(out.status, dout.status, RT), down(out.start_tick, dout.start_tick, RT * 8);
+    down(out.done_tick, dout.done_tick, RT * 8), down(out.stats, dout.stats, R * sizeof(fognet_rep_stats));
+    down(out.hist, dout.hist, FOGNET_HIST_METRICS * FOGNET_HIST_BINS * sizeof(int64_t));
+  }
+  for (const void* p : {(const void*)din.arrive_tick, (const void*)din.req_mips, (const void*)din.mips,
+                        (const void*)din.dl_tick, (const void*)din.ul_tick, (const void*)din.init_adv_tick,
+                        (const void*)(in.p_busy_w ? din.p_busy_w : nullptr), (const void*)(in.p_busy_w ? din.p_idle_w : nullptr),
+                        (const void*)d_assign, (const void*)dout.node, (const void*)dout.status,
+                        (const void*)dout.start_tick, (const void*)dout.done_tick, (const void*)dout.stats,
+                        (const void*)dout.hist})
+    if (p) (void)hipFree(const_cast<void*>(p));
+  return rc;
+}
+
+// --assign: names the rule among the run attributes of a result file the library wrote
+void add_run_attr(const std::string& path, const std::string& name, const std::string& value) {
+  std::ifstream f(path);
+  if (!f) die("cannot read back " + path);
+  std::stringstream all;
+  std::string line;
+  bool done = false;
+  while (std::getline(f, line)) {
+    all << line << "\n";
+    if (!done && line.rfind("run ", 0) == 0) {
+      all << "attr " << name << " " << value << "\n";
+      done = true;
+    }
+  }
+  f.close();
+  std::ofstream w(path, std::ios::trunc);
+  w << all.str();
+  if (!w) die("cannot write " + path);
+}
+
 int run_v3(const Options& o, fognet_batch_in in, const std::string& network, const std::string& run_id,
-           const UserSide* us = nullptr) {
+           const UserSide* us = nullptr, int r0 = 0) {
   const size_t RT = (size_t)in.R * (size_t)in.T;
   std::vector<int32_t> node(RT);
   std::vector<uint8_t> status(RT);
@@ -801,11 +892,12 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
     local_err = "fognet_create: no gfx950 device " + std::to_string(o.device);
     ctx = nullptr;
   } else {
-    const int rc = fognet_run_batch(ctx, &in, &out);
+    const int rc = o.assign ? run_assigned_host(ctx, in, make_assignment(o, in, r0), out) : fognet_run_batch(ctx, &in, &out);
     bool replayed = true;
     for (const fognet_rep_stats& s : stats) replayed = replayed && s.status != -1;
     if (rc != FOGNET_OK && !replayed)
-      local_err = std::string("fognet_run_batch: ") + fognet_status_string(rc) + ": " + fognet_last_error(ctx);
+      local_err = std::string(o.assign ? "fognet_run_assigned_dev: " : "fognet_run_batch: ") + fognet_status_string(rc) +
+                  ": " + fognet_last_error(ctx);
   }
   if (o.comm_id.empty() && !local_err.empty()) die(local_err);
   if (!o.comm_id.empty()) {  // a failed rank reports instead of dying: no rank may be left in RCCL
@@ -825,6 +917,7 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
     return local_failed ? 1 : 0;
   }
   if (!o.sca.empty()) check(fognet_write_sca(o.sca.c_str(), run_id.c_str(), network.c_str(), &job, hist.data()), "sca");
+  if (!o.sca.empty() && o.assign) add_run_attr(o.sca, "assign", assign_name(o));
   if (!o.sca.empty() && o.node_stats) append_node_stats(o, ctx, in, out, network, run_id);
   if (!o.sca.empty() && o.user_stats && us) append_user_stats(o, ctx, in, out, *us, network, run_id);
   if (!o.vec.empty()) {  // replication 0's vectors (a failed replication has no complete outputs)
@@ -833,12 +926,13 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
     check(fognet_write_vec(o.vec.c_str(), run_id.c_str(), network.c_str(), in.T, in.N, in.arrive_tick, in.dl_tick,
                            node.data(), status.data(), start.data(), nullptr),
           "vec");
+    if (o.assign) add_run_attr(o.vec, "assign", assign_name(o));
     if (o.vec_users && us) append_user_vectors(o, ctx, in, out, *us, network, run_id);
   }
   if (!o.quiet) {
     std::printf("policy=%s R=%d T=%d N=%d decisions=%" PRId64 " queued=%" PRId64 " started=%" PRId64
                 " failed_reps=%" PRId64 " makespan_ticks=%" PRId64 " max_pending=%" PRId64 "\n",
-                in.policy == FOGNET_POLICY_EXT_LAT ? "EXT_LAT" : "REF_V3", in.R, in.T, in.N, job.n_tasks, job.n_queued,
+                o.assign ? ("assign:" + assign_name(o)).c_str() : in.policy == FOGNET_POLICY_EXT_LAT ? "EXT_LAT" : "REF_V3", in.R, in.T, in.N, job.n_tasks, job.n_queued,
                 job.n_started, job.n_failed, job.last_tick, job.max_pending);
     std::vector<int64_t> per(in.N, 0);  // completed replications only (a failed one stops mid-trace)
     for (int32_t r = 0; r < in.R; ++r) {
@@ -982,6 +1076,7 @@ int main(int argc, char** argv) {
   if (!v2 && sc.broker_type != "BrokerBaseApp3" && sc.broker_type != "BrokerBaseAppHip")
     die("broker module " + sc.broker_type + " is not on the engine's path (BrokerBaseApp3, BrokerBaseApp2)");
   if (v2 && o.policy_set) die("--policy applies to BrokerBaseApp3 runs");
+  if (v2 && o.assign) die("--assign applies to BrokerBaseApp3 runs (the BrokerBaseApp2 broker serves tasks itself)");
   if (v2 && o.user_stats)
     die("--user-stats applies to BrokerBaseApp3 runs (the BrokerBaseApp2 model has no closed form for the user signals)");
   if (v2 && o.vec_users)
@@ -1063,5 +1158,5 @@ int main(int argc, char** argv) {
     if (o.world > 1) die("BrokerBaseApp2 replays run on one GPU (--world 1)");
     return run_v2(o, sc, T, arrive, req, dl, ul, first_adv, run_id);
   }
-  return run_v3(o, in, sc.network, run_id, o.user_stats || o.vec_users ? &us : nullptr);
+  return run_v3(o, in, sc.network, run_id, o.user_stats || o.vec_users ? &us : nullptr, r0);
 }

@@ -453,6 +453,15 @@ int32_t signal_vectors_sort_lds_max();
 hipError_t launch_signal_vectors(const ReplayArgs& a, const UserLinks& users, int32_t r0, int32_t Rv,
                                  const fognet_signal_vectors& vec, int64_t* n_unassigned, uint32_t* cursor,
                                  bool force_hbm, int stages, hipStream_t s);
+// Assigned replay (replay_assigned.hip): the node model under the caller's decisions assign [R][T],
+// a validation + count kernel and one wavefront per replication over tiles of 64 tasks.  Fills
+// a.out_node/out_status/out_start/out_done and the replay fields of a.out_stats; stats: the whole
+// record, a.hist and the energy model as well.  Up to replay_assigned_lds_max() nodes the per-node
+// carries live in LDS unless force_hbm; w: the workspace (AssignedWs).  stages: 1 stops after the
+// validation + count kernel (timing), 2: the whole pass.
+int32_t replay_assigned_lds_max();
+hipError_t launch_replay_assigned(const ReplayArgs& a, const int32_t* assign, const AssignedWs& w, bool stats,
+                                  bool force_hbm, int stages, hipStream_t s);
 // v2 model replay (replay_v2.hip)
 size_t replay_v2_workspace_bytes(int32_t R, int32_t T, int32_t N, int32_t q_log2);
 hipError_t launch_replay_v2(const fognet_v2_in& in, const fognet_v2_out& out, void* workspace, int32_t q_log2,

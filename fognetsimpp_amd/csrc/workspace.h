@@ -95,4 +95,24 @@ inline size_t signal_vectors_ws(VecWs& w, size_t Rv, size_t V, WsCursor& v) {
   return v.off;
 }
 
+// Assigned replay (replay_assigned.hip): [refusal flags | node offsets | advert rows || carries].
+// off: the exclusive scan of the tasks per node, one row of N + 1 per replication; adv: every
+// task's completion advert tick, grouped by node in trace order (row off[k] + rank); the five
+// carry arrays hold what a node carries from tile to tile where it does not fit in LDS (carry_n
+// = R * N above the kernel's LDS capacity or when the workspace layout is forced, else 0).
+struct AssignedWs {
+  int32_t* bad;      // [R] 1: refused by the validation pass
+  uint32_t* off;     // [R][N + 1]
+  int64_t* adv;      // [R][T]
+  int64_t* c_done;   // [R][N] the carries (replay_assigned.hip says what each holds)
+  uint64_t* c_busy;
+  uint32_t *c_S, *c_rank, *c_head;
+};
+
+inline size_t assigned_ws(AssignedWs& w, size_t R, size_t T, size_t N, size_t carry_n, WsCursor& v) {
+  v(w.bad, R), v(w.off, R * (N + 1)), v(w.adv, R * T);
+  v(w.c_done, carry_n), v(w.c_busy, carry_n), v(w.c_S, carry_n), v(w.c_rank, carry_n), v(w.c_head, carry_n);
+  return v.off;
+}
+
 }  // namespace fognet

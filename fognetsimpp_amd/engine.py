@@ -337,6 +337,70 @@ def run_batch(ctx: Context, trace: dict, out: BatchResult | None = None, ring_ca
     return out
 
 
+def run_assigned(ctx: Context, trace: dict, assign: torch.Tensor, out: BatchResult | None = None,
+                 stats: bool = True, hist: bool = False, energy: bool = False, stream=None) -> BatchResult:
+    """The node model under the caller's decisions (fognet_run_assigned_dev): task i of
+    replication r goes to node ``assign[r, i]`` (int32 [R, T] on the trace's device: a policy
+    evaluated in PyTorch, recorded decisions, :func:`assign_round_robin`, :func:`assign_random`).
+    No broker decides; each node is a FIFO single server over the tasks sent to it.
+
+    ``trace``: as :func:`run_batch` (``down`` and the power model included; ``region`` is not
+    read).  ``stats=False``: fognet_replay_assigned_dev, which fills the per-task arrays and the
+    record's status / n_tasks / max_pending / events only.  ``hist`` / ``energy``: allocate the
+    job histogram / the per-node energy rows when ``out`` is None (``energy`` needs the power
+    model in the trace).  ``out.node`` receives the assignment and may be ``assign`` itself.
+    The result serves :func:`node_stats`, :func:`per_user_stats`, :func:`user_stats` and
+    :func:`signal_vectors` as a REF_V3 replay's does.  A replication with a bad input (an
+    ``assign`` entry outside [0, N) among them) has status FOGNET_ERR_ARG in its record."""
+    arrive, req = trace["arrive"], trace["req"]
+    R, T = arrive.shape
+    mips = trace["mips"]
+    N = mips.shape[-1]
+    stride = N if mips.dim() == 2 else 0
+    power = trace.get("p_busy") is not None
+    down = trace.get("down")
+    for k in ("dl", "ul", "init") + (("p_busy", "p_idle") if power else ()) + (("down",) if down is not None else ()):
+        if tuple(trace[k].shape) != tuple(mips.shape):
+            raise FognetError(_abi.FOGNET_ERR_ARG, f"{k} has shape {tuple(trace[k].shape)}, mips {tuple(mips.shape)}")
+    if tuple(req.shape) != (R, T) or (mips.dim() == 2 and mips.shape[0] != R):
+        raise FognetError(_abi.FOGNET_ERR_ARG, "trace arrays disagree on R/T")
+    if (not isinstance(assign, torch.Tensor) or assign.dtype != torch.int32 or tuple(assign.shape) != (R, T)
+            or assign.device != arrive.device or not assign.is_contiguous()):
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"assign: a contiguous int32 [{R}, {T}] tensor on {arrive.device}")
+    if energy and not power:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "energy needs the power model (p_busy / p_idle) in the trace")
+    if out is None:
+        out = allocate_outputs(R, T, arrive.device, N=N, energy=energy, hist=hist)
+    if out.node is None or tuple(out.node.shape) != (R, T) or out.stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "run_assigned needs the per-task output arrays [R, T] and R records")
+    bi = _abi.BatchIn(R, T, N, _abi.FOGNET_POLICY_REF_V3, stride, 0,
+                      _ptr(arrive), _ptr(req), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
+                      _ptr(trace["init"]), _ptr(trace.get("p_busy")), _ptr(trace.get("p_idle")), _ptr(down),
+                      None, 0, 0, 0)
+    bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick),
+                       _ptr(out.stats), _ptr(out.node_energy), _ptr(out.hist), _ptr(out.escalated))
+    s = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr(arrive.device)
+    fn = ctx._lib.fognet_run_assigned_dev if stats else ctx._lib.fognet_replay_assigned_dev
+    ctx.check(fn(ctx.handle, C.byref(bi), _ptr(assign), C.byref(bo), s), "run_assigned")
+    out.policy = _abi.FOGNET_POLICY_REF_V3  # what the passes over the outputs go by
+    out.hier_up_tick = 0
+    return out
+
+
+def assign_round_robin(R: int, T: int, N: int, device) -> torch.Tensor:
+    """Task i to node i mod N in every replication: int32 [R, T] on ``device``."""
+    row = torch.arange(T, dtype=torch.int64, device=device).remainder(N).to(torch.int32)
+    return row.unsqueeze(0).expand(R, T).contiguous()
+
+
+def assign_random(R: int, T: int, N: int, seed: int, device) -> torch.Tensor:
+    """Uniformly random nodes from a torch generator seeded with ``seed`` on ``device``:
+    int32 [R, T].  (The driver's ``--assign random`` draws from std::mt19937_64 instead.)"""
+    g = torch.Generator(device=device)
+    g.manual_seed(int(seed))
+    return torch.randint(0, N, (R, T), generator=g, device=device, dtype=torch.int32)
+
+
 def run_generated(ctx: Context, seed: int, R: int, T: int, N: int, mean_gap_ticks, lat_scale, r0: int = 0,
                   req_lo: int = 1000, req_hi: int = 64000, out: BatchResult | None = None, ring_capacity: int = 0,
                   policy: str | int = "REF_V3", power=None, hist: bool = True, energy: bool = False,

@@ -350,7 +350,10 @@ typedef struct fognet_batch_out {
  *     touched, no initialisation needed; rows at and past offset[V] keep what they held; a
  *     failed replication's offsets are all 0 and none of its rows is written.
  *   escalated likewise: 1-B alignment, nothing outside [R][T] touched, no initialisation
- *     needed; a failed replication's row is undefined, like its other per-task rows. */
+ *     needed; a failed replication's row is undefined, like its other per-task rows.
+ *   The assignment (fognet_replay_assigned_dev's and fognet_run_assigned_dev's assign [R][T])
+ *     likewise: 4-B alignment, nothing outside [R][T] read; it is never written, unless the caller
+ *     passes the same pointer as out->node, which then holds the same values afterwards. */
 
 /* count / min / max / exact signed 128-bit sum and 192-bit sum of squares of a
  * signal's raw emitted values (min_raw = INT64_MAX, max_raw = INT64_MIN when
@@ -537,6 +540,51 @@ int fognet_rep_stats_dev(fognet_ctx *ctx, const fognet_batch_in *in, fognet_batc
 /* Host-buffer variant: copies in, replays, copies out, synchronises.  Returns
  * the first non-OK replication status, if any. */
 int fognet_run_batch(fognet_ctx *ctx, const fognet_batch_in *in, fognet_batch_out *out);
+
+/* Assigned replay: the node model under the CALLER's decisions.  Task i of replication r goes
+ * to node assign[r][i] (device, [R][T]); no broker decides, so policy, ring_capacity, region and
+ * the hier_* fields of `in` are not read.  Read: R, T, N, node_stride, arrive_tick, req_mips,
+ * mips, dl_tick, ul_tick, init_adv_tick (its preconditions only), flags, and p_busy_w / p_idle_w /
+ * down_tick as fognet_run_batch_dev reads them.
+ * The node model (ComputeBrokerApp3.cc:269-320), with k = assign[i],
+ * s = (req_i / mips_k) * 10^12 ticks (int division), a = arrive_i + dl_k and p the previous task
+ * of the trace on node k: the first task on a node has status 5 and start = a; otherwise start =
+ * max(a, done_p), and status is 5 iff a > done_p, or a == done_p and dl_k < s_p (the completion's
+ * timer was then inserted before the arrival event), else 4; done = start + s.
+ * down_tick: a task with a >= down_k has status 9, start = done = -1 and takes no place in the
+ * queue; a computed start >= down_k becomes -1, and so does a computed done >= down_k (the crash
+ * precedes its tick's events and cancels the timer).
+ * stats[r].max_pending: the maximum over tasks of 1 + the earlier tasks on the same node whose
+ * completion advert (done + ul_k) has not reached the broker strictly before arrive_i (a task that
+ * never completes stays pending); stats[r].events: 2N + 4 per task, 2 for a task that never
+ * completes.
+ * Written: all four per-task arrays (required; out->node receives the assignment and may be the
+ * same pointer as assign), escalated (if given: 0), stats[r].{status, n_tasks, max_pending,
+ * events}; fognet_run_assigned_dev completes the record, hist and node_energy_j as
+ * fognet_run_batch_dev does.  Afterwards the same `in` with policy = FOGNET_POLICY_REF_V3 serves
+ * fognet_node_stats_dev, fognet_per_user_stats_dev, fognet_user_stats_dev and
+ * fognet_signal_vectors_dev.
+ * A replication with a bad input is refused as a whole, before its first decision: status
+ * FOGNET_ERR_ARG and the empty-set record (n_tasks = 0, events = 0; "Buffers" above); its
+ * neighbours are untouched.  Bad inputs: an assign entry outside [0, N), decreasing arrive_tick,
+ * negative req, mips <= 0, the init_adv_tick / down_tick preconditions of fognet_batch_in, an
+ * arrival past 2^61 ticks, and a task that starts with a service time of 2^22 s or more or a
+ * completion past 2^61 ticks (intermediate sums saturate, they never wrap).
+ * Refused calls: a statistics-only `out`, a NULL assign with R * T > 0, NULL stats
+ * (FOGNET_ERR_ARG); N > 2^20, the power model together with down_tick (FOGNET_ERR_UNSUPPORTED).
+ * R = 0 and T = 0 succeed.  Both calls only enqueue and use the context's workspace (8 B per
+ * task, 4 B per replication and node; 28 B more per replication and node above
+ * FOGNET_ASSIGNED_LDS_NODES nodes).  The trace is walked in tiles of FOGNET_ASSIGNED_TILE tasks.
+ * FOGNET_ASSIGNED=hbm (environment, testing): the per-node counts and carries live in the
+ * workspace for every N, as they do above FOGNET_ASSIGNED_LDS_NODES nodes; the results are
+ * identical.  FOGNET_ASSIGNED_STAGES=1 (timing only): stop after the validation and count stage;
+ * no output is written then. */
+#define FOGNET_ASSIGNED_TILE 64
+#define FOGNET_ASSIGNED_LDS_NODES 1024
+int fognet_replay_assigned_dev(fognet_ctx *ctx, const fognet_batch_in *in, const int32_t *assign,
+                               fognet_batch_out *out, void *hip_stream);
+int fognet_run_assigned_dev(fognet_ctx *ctx, const fognet_batch_in *in, const int32_t *assign,
+                            fognet_batch_out *out, void *hip_stream);
 
 /* User-side signals from a finished replay (fognet_replay_dev or
  * fognet_run_batch_dev on the same stream): device pointers in `in` (trace,
