@@ -9,7 +9,7 @@
 // From the ini it reads the keys the reference modules read through par():
 //   network                                      (module path prefix)
 //   <net>.BaseBroker.udpApp[0].typename / MIPS   BrokerBaseApp3 -> FOGNET_POLICY_REF_V3 on
-//                                                fognet_run_batch; BrokerBaseApp2 -> the v2
+//                                                fognet_run_batch_dev; BrokerBaseApp2 -> the v2
 //                                                model replay (fognet_run_v2_dev)
 //   <net>.ComputeBroker<k>.udpApp[0].MIPS        ComputeBrokerApp3.cc:43 / ComputeBrokerApp2
 //   <net>.ComputeBroker<k>.udpApp[0].startTime   ComputeBrokerApp3.cc:54 (node CONNECT)
@@ -34,12 +34,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <memory>
+#include <optional>
 #include <random>
 #include <sstream>
 #include <string>
 #include <chrono>
 #include <thread>
-#include <type_traits>
 #include <vector>
 
 #include "fognet_hip.h"
@@ -51,6 +52,7 @@ constexpr int64_t kTick = 1;              // simtime_t raw unit: 1 ps
 constexpr int64_t kMs = 1000000000LL;     // ticks per millisecond
 constexpr int64_t kSec = 1000000000000LL;  // ticks per second
 constexpr int64_t kNoTick = INT64_MIN;
+constexpr size_t kHistLen = (size_t)FOGNET_HIST_METRICS * FOGNET_HIST_BINS;  // the job histogram, in int64
 
 [[noreturn]] void die(const std::string& msg) {
   std::fprintf(stderr, "fognet_replay: %s\n", msg.c_str());
@@ -420,10 +422,6 @@ void check_ctx(fognet_ctx* ctx, int rc, const char* what) {
   if (rc != FOGNET_OK) die(std::string(what) + ": " + fognet_status_string(rc) + ": " + fognet_last_error(ctx));
 }
 
-void hip_check(hipError_t e, const char* what) {
-  if (e != hipSuccess) die(std::string(what) + ": " + hipGetErrorString(e));
-}
-
 // The publish traces of R replications (glibc seeds seed .. seed + R - 1).
 // Returns T (equal for every replication: the seed only changes MIPSRequired).
 // Replications r0 .. r0 + n - 1 of the job (glibc seed o.seed + r).
@@ -583,7 +581,6 @@ Options parse_args(int argc, char** argv) {
 
 // ---------------------------------------------------------------- runs
 
-// BrokerBaseApp3 + ComputeBrokerApp3 (the batch engine, host-buffer entry point).
 // The job record of all ranks (fognet_allreduce_stats over the library's RCCL
 // communicator); the 128-byte id goes from rank 0 to the others through the
 // file o.comm_id (written atomically, removed once every rank has joined).
@@ -627,6 +624,85 @@ void remove_rank_files(const Options& o) {
   for (int k = 0; k < o.world; ++k) std::remove((o.comm_id + ".rank" + std::to_string(k)).c_str());
 }
 
+// Device memory that is freed with its owner.  The first hipMalloc / hipMemcpy that fails is kept in err()
+// and nothing is allocated or copied after it (alloc and copy return null), so a caller looks at err() once
+// before it hands the pointers on.
+class DeviceMem {
+ public:
+  DeviceMem() = default;
+  DeviceMem(const DeviceMem&) = delete;
+  DeviceMem& operator=(const DeviceMem&) = delete;
+  ~DeviceMem() { for (void* p : owned_) (void)hipFree(p); }
+  const std::string& err() const { return err_; }
+  void must() const { if (!err_.empty()) die(err_); }
+  template <class T>
+  T* alloc(size_t n) {
+    void* p = nullptr;
+    if (!err_.empty() || !ok(hipMalloc(&p, std::max<size_t>(1, n * sizeof(T))), "hipMalloc")) return nullptr;
+    owned_.push_back(p);
+    return static_cast<T*>(p);
+  }
+  template <class T>
+  T* copy(const T* h, size_t n) {
+    T* p = alloc<T>(n);
+    if (p && n) ok(hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
+    return p;
+  }
+  template <class T>
+  T* copy(const std::vector<T>& h) { return copy(h.data(), h.size()); }
+  template <class T>
+  void fetch(T* h, const T* d, size_t n) {
+    if (err_.empty() && n) ok(hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost), "hipMemcpy");
+  }
+  void sync() { if (err_.empty()) ok(hipDeviceSynchronize(), "hipDeviceSynchronize"); }
+
+ private:
+  bool ok(hipError_t e, const char* what) {
+    if (e != hipSuccess) err_ = std::string(what) + ": " + hipGetErrorString(e);
+    return e == hipSuccess;
+  }
+  std::vector<void*> owned_;
+  std::string err_;
+};
+
+// The one device copy of a BrokerBaseApp3 run: the trace of the host batch `in` (the power model when it has
+// one) and the outputs of the replay, which the passes over the finished replay then read where they are.
+struct DeviceBatch : DeviceMem {
+  fognet_batch_in din;     // `in` with device pointers
+  fognet_batch_out dout{};  // per-task arrays, records and the histogram (it is added to: starts from host.hist)
+
+  DeviceBatch(const fognet_batch_in& in, const fognet_batch_out& host) : din(in) {
+    const size_t R = (size_t)in.R, RT = R * (size_t)in.T, NRN = (in.node_stride ? R : 1) * (size_t)in.N;
+    din.arrive_tick = copy(in.arrive_tick, RT), din.req_mips = copy(in.req_mips, RT);
+    din.mips = copy(in.mips, NRN), din.dl_tick = copy(in.dl_tick, NRN), din.ul_tick = copy(in.ul_tick, NRN);
+    din.init_adv_tick = copy(in.init_adv_tick, NRN);
+    if (in.p_busy_w) din.p_busy_w = copy(in.p_busy_w, NRN), din.p_idle_w = copy(in.p_idle_w, NRN);
+    dout.node = alloc<int32_t>(RT), dout.status = alloc<uint8_t>(RT), dout.start_tick = alloc<int64_t>(RT);
+    dout.done_tick = alloc<int64_t>(RT), dout.stats = alloc<fognet_rep_stats>(R);
+    dout.hist = copy(host.hist, kHistLen);
+  }
+
+  // the finished replay's outputs, once everything enqueued on the device is done; a failure is in err()
+  void download(const fognet_batch_out& host) {
+    sync();
+    const size_t R = (size_t)din.R, RT = R * (size_t)din.T;
+    fetch(host.node, dout.node, RT), fetch(host.status, dout.status, RT), fetch(host.start_tick, dout.start_tick, RT);
+    fetch(host.done_tick, dout.done_tick, RT), fetch(host.stats, dout.stats, R), fetch(host.hist, dout.hist, kHistLen);
+  }
+
+  // What a pass over the finished replay is handed: no power model, no crash ticks, no histogram.
+  fognet_batch_in pass_in() const {
+    fognet_batch_in p = din;
+    p.p_busy_w = p.p_idle_w = nullptr, p.down_tick = nullptr;
+    return p;
+  }
+  fognet_batch_out pass_out() const {
+    fognet_batch_out p = dout;
+    p.hist = nullptr;
+    return p;
+  }
+};
+
 void exchange_stats(const Options& o, fognet_ctx* ctx, fognet_job_stats* job, std::vector<int64_t>& hist) {
   uint8_t id[FOGNET_COMM_ID_BYTES];
   if (o.rank == 0) {
@@ -653,58 +729,33 @@ void exchange_stats(const Options& o, fognet_ctx* ctx, fognet_job_stats* job, st
     std::remove(o.comm_id.c_str());
     remove_rank_files(o);
   }
-  int64_t* d_hist = nullptr;
-  const size_t hb = hist.size() * sizeof(int64_t);
-  hip_check(hipMalloc((void**)&d_hist, hb), "hipMalloc");
-  hip_check(hipMemcpy(d_hist, hist.data(), hb, hipMemcpyHostToDevice), "hipMemcpy");
+  DeviceMem mem;
+  int64_t* d_hist = mem.copy(hist);
+  mem.must();
   check_ctx(ctx, fognet_allreduce_stats(ctx, comm, job, d_hist, nullptr), "fognet_allreduce_stats");
-  hip_check(hipMemcpy(hist.data(), d_hist, hb, hipMemcpyDeviceToHost), "hipMemcpy");
-  (void)hipFree(d_hist);
+  mem.fetch(hist.data(), d_hist, hist.size());
+  mem.must();
   fognet_comm_destroy(comm);
 }
 
-template <class T>
-T* dev_copy(const std::vector<T>& h) {
-  void* p = nullptr;
-  hip_check(hipMalloc(&p, std::max<size_t>(1, h.size() * sizeof(T))), "hipMalloc");
-  if (!h.empty()) hip_check(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
-  return static_cast<T*>(p);
-}
-
-template <class T>
-T* dev_alloc(size_t n) {
-  void* p = nullptr;
-  hip_check(hipMalloc(&p, std::max<size_t>(1, n * sizeof(T))), "hipMalloc");
-  return static_cast<T*>(p);
-}
-
-// --node-stats: the per-node records of the finished replay (fognet_node_stats_dev over device copies of
-// the trace and the per-task outputs), reduced over the replications (fognet_reduce_node_stats_dev) and
-// appended to the job's .sca, one block per fog node module.
-void append_node_stats(const Options& o, fognet_ctx* ctx, const fognet_batch_in& in, const fognet_batch_out& out,
-                       const std::string& network, const std::string& run_id) {
-  const size_t R = (size_t)in.R, RT = R * (size_t)in.T, N = (size_t)in.N, NRN = (in.node_stride ? R : 1) * N;
-  auto up = [](const auto* h, size_t n) {
-    return dev_copy(std::vector<std::remove_cv_t<std::remove_pointer_t<decltype(h)>>>(h, h + n));
-  };
-  fognet_batch_in din = in;
-  din.arrive_tick = up(in.arrive_tick, RT), din.req_mips = up(in.req_mips, RT), din.mips = up(in.mips, NRN);
-  din.dl_tick = up(in.dl_tick, NRN), din.ul_tick = up(in.ul_tick, NRN), din.init_adv_tick = up(in.init_adv_tick, NRN);
-  din.p_busy_w = din.p_idle_w = nullptr;
-  din.down_tick = nullptr;
-  fognet_batch_out dout{up(out.node, RT), up(out.status, RT), up(out.start_tick, RT), up(out.done_tick, RT),
-                        up(out.stats, R), nullptr, nullptr};
-  fognet_node_stats* d_nodes = dev_alloc<fognet_node_stats>(R * N);
-  fognet_node_stats* d_job = dev_alloc<fognet_node_stats>(N);
+// --node-stats: the per-node records (fognet_node_stats_dev), reduced over the replications
+// (fognet_reduce_node_stats_dev): one .sca block per fog node module.
+void append_node_stats(const Options& o, fognet_ctx* ctx, const DeviceBatch& db, const std::string& network,
+                       const std::string& run_id) {
+  const fognet_batch_in din = db.pass_in();
+  const fognet_batch_out dout = db.pass_out();
+  const size_t R = (size_t)din.R, N = (size_t)din.N;
+  DeviceMem mem;
+  fognet_node_stats* d_nodes = mem.alloc<fognet_node_stats>(R * N);
+  fognet_node_stats* d_job = mem.alloc<fognet_node_stats>(N);
+  mem.must();
   check_ctx(ctx, fognet_node_stats_dev(ctx, &din, &dout, d_nodes, nullptr), "fognet_node_stats_dev");
-  check_ctx(ctx, fognet_reduce_node_stats_dev(ctx, d_nodes, dout.stats, in.R, in.N, d_job, nullptr),
+  check_ctx(ctx, fognet_reduce_node_stats_dev(ctx, d_nodes, dout.stats, din.R, din.N, d_job, nullptr),
             "fognet_reduce_node_stats_dev");
   std::vector<fognet_node_stats> nodes(N);
-  hip_check(hipMemcpy(nodes.data(), d_job, N * sizeof(fognet_node_stats), hipMemcpyDeviceToHost), "hipMemcpy");
-  const void* bufs[] = {din.arrive_tick, din.req_mips, din.mips, din.dl_tick, din.ul_tick, din.init_adv_tick,
-                        dout.node, dout.status, dout.start_tick, dout.done_tick, dout.stats, d_nodes, d_job};
-  for (const void* b : bufs) (void)hipFree(const_cast<void*>(b));
-  check(fognet_write_sca_nodes(o.sca.c_str(), run_id.c_str(), network.c_str(), in.N, nodes.data(), nullptr, 1), "sca nodes");
+  mem.fetch(nodes.data(), d_job, N);
+  mem.must();
+  check(fognet_write_sca_nodes(o.sca.c_str(), run_id.c_str(), network.c_str(), din.N, nodes.data(), nullptr, 1), "sca nodes");
 }
 
 // what --user-stats adds to a BrokerBaseApp3 run: the users in --users order and every publish's user
@@ -713,41 +764,32 @@ struct UserSide {
   std::vector<int32_t> user_of;      // [R][T]
 };
 
-// --user-stats: the per-user records of the finished replay (fognet_per_user_stats_dev over device copies
-// of the trace, the per-task outputs and user_of, with the links --user-ul / --user-dl shared by all users),
-// reduced over the replications (fognet_reduce_user_stats_dev) and appended to the job's .sca, one block per
-// user module plus the broker's delay.
-void append_user_stats(const Options& o, fognet_ctx* ctx, const fognet_batch_in& in, const fognet_batch_out& out,
-                       const UserSide& us, const std::string& network, const std::string& run_id) {
-  const size_t R = (size_t)in.R, RT = R * (size_t)in.T, N = (size_t)in.N, NRN = (in.node_stride ? R : 1) * N;
+// --user-stats: the per-user records (fognet_per_user_stats_dev; the links --user-ul / --user-dl are shared by
+// all users), reduced over the replications (fognet_reduce_user_stats_dev): one .sca block per user module plus
+// the broker's delay.
+void append_user_stats(const Options& o, fognet_ctx* ctx, const DeviceBatch& db, const UserSide& us,
+                       const std::string& network, const std::string& run_id) {
+  const fognet_batch_in din = db.pass_in();
+  fognet_batch_out dout = db.pass_out();
+  dout.start_tick = nullptr;  // not read by this pass
+  const size_t R = (size_t)din.R;
   const int32_t U = (int32_t)us.modules.size();
-  auto up = [](const auto* h, size_t n) {
-    return dev_copy(std::vector<std::remove_cv_t<std::remove_pointer_t<decltype(h)>>>(h, h + n));
-  };
-  fognet_batch_in din = in;
-  din.arrive_tick = up(in.arrive_tick, RT), din.req_mips = up(in.req_mips, RT), din.mips = up(in.mips, NRN);
-  din.dl_tick = up(in.dl_tick, NRN), din.ul_tick = up(in.ul_tick, NRN), din.init_adv_tick = up(in.init_adv_tick, NRN);
-  din.p_busy_w = din.p_idle_w = nullptr;
-  din.down_tick = nullptr;
-  fognet_batch_out dout{up(out.node, RT), up(out.status, RT), nullptr, up(out.done_tick, RT), up(out.stats, R),
-                        nullptr, nullptr};
-  int32_t* d_user_of = dev_copy(us.user_of);
-  int64_t* d_ul = dev_copy(std::vector<int64_t>(U, o.user_ul));
-  int64_t* d_dl = dev_copy(std::vector<int64_t>(U, o.user_dl));
-  fognet_user_stats* d_users = dev_alloc<fognet_user_stats>(R * (size_t)U);
-  fognet_user_stats* d_job = dev_alloc<fognet_user_stats>(U);
-  int64_t* d_un = dev_alloc<int64_t>(R);
+  DeviceMem mem;
+  int32_t* d_user_of = mem.copy(us.user_of);
+  int64_t* d_ul = mem.copy(std::vector<int64_t>(U, o.user_ul));
+  int64_t* d_dl = mem.copy(std::vector<int64_t>(U, o.user_dl));
+  fognet_user_stats* d_users = mem.alloc<fognet_user_stats>(R * (size_t)U);
+  fognet_user_stats* d_job = mem.alloc<fognet_user_stats>(U);
+  int64_t* d_un = mem.alloc<int64_t>(R);
+  mem.must();
   check_ctx(ctx, fognet_per_user_stats_dev(ctx, &din, &dout, d_user_of, U, 0, d_ul, d_dl, d_users, d_un, nullptr),
             "fognet_per_user_stats_dev");
-  check_ctx(ctx, fognet_reduce_user_stats_dev(ctx, d_users, dout.stats, in.R, U, d_job, nullptr),
+  check_ctx(ctx, fognet_reduce_user_stats_dev(ctx, d_users, dout.stats, din.R, U, d_job, nullptr),
             "fognet_reduce_user_stats_dev");
   std::vector<fognet_user_stats> users(U);
   std::vector<int64_t> un(R);
-  hip_check(hipMemcpy(users.data(), d_job, (size_t)U * sizeof(fognet_user_stats), hipMemcpyDeviceToHost), "hipMemcpy");
-  hip_check(hipMemcpy(un.data(), d_un, R * sizeof(int64_t), hipMemcpyDeviceToHost), "hipMemcpy");
-  const void* bufs[] = {din.arrive_tick, din.req_mips, din.mips, din.dl_tick, din.ul_tick, din.init_adv_tick, dout.node,
-                        dout.status, dout.done_tick, dout.stats, d_user_of, d_ul, d_dl, d_users, d_job, d_un};
-  for (const void* b : bufs) (void)hipFree(const_cast<void*>(b));
+  mem.fetch(users.data(), d_job, (size_t)U), mem.fetch(un.data(), d_un, R);
+  mem.must();
   for (size_t r = 0; r < R; ++r)
     if (un[r] != 0)
       die("--user-stats: replication " + std::to_string(r) + " has " + std::to_string(un[r]) +
@@ -758,47 +800,36 @@ void append_user_stats(const Options& o, fognet_ctx* ctx, const fognet_batch_in&
         "sca users");
 }
 
-// --vec-users: replication 0's user-side vectors (fognet_signal_vectors_dev over device copies of the trace,
-// the per-task outputs and user_of, with the links --user-ul / --user-dl shared by all users), appended to the
-// .vec fognet_write_vec wrote: the broker's delay and every user module's latency, latencyH1 and taskTime.
-void append_user_vectors(const Options& o, fognet_ctx* ctx, const fognet_batch_in& in, const fognet_batch_out& out,
-                         const UserSide& us, const std::string& network, const std::string& run_id) {
-  const size_t R = (size_t)in.R, RT = R * (size_t)in.T, N = (size_t)in.N, NRN = (in.node_stride ? R : 1) * N;
+// --vec-users: replication 0's user-side vectors (fognet_signal_vectors_dev; links as for --user-stats),
+// appended to the .vec fognet_write_vec wrote: the broker's delay and every user module's latency, latencyH1
+// and taskTime.
+void append_user_vectors(const Options& o, fognet_ctx* ctx, const DeviceBatch& db, const UserSide& us,
+                         const std::string& network, const std::string& run_id) {
+  const fognet_batch_in din = db.pass_in();
+  const fognet_batch_out dout = db.pass_out();
+  const size_t N = (size_t)din.N;
   const int32_t U = (int32_t)us.modules.size();
-  const size_t V = N + 1 + 3 * (size_t)U, cap = 6 * (size_t)in.T;
-  auto up = [](const auto* h, size_t n) {
-    return dev_copy(std::vector<std::remove_cv_t<std::remove_pointer_t<decltype(h)>>>(h, h + n));
-  };
-  fognet_batch_in din = in;
-  din.arrive_tick = up(in.arrive_tick, RT), din.req_mips = up(in.req_mips, RT), din.mips = up(in.mips, NRN);
-  din.dl_tick = up(in.dl_tick, NRN), din.ul_tick = up(in.ul_tick, NRN), din.init_adv_tick = up(in.init_adv_tick, NRN);
-  din.p_busy_w = din.p_idle_w = nullptr;
-  din.down_tick = nullptr;
-  fognet_batch_out dout{up(out.node, RT), up(out.status, RT), up(out.start_tick, RT), up(out.done_tick, RT),
-                        up(out.stats, R), nullptr, nullptr};
-  int32_t* d_user_of = dev_copy(us.user_of);
-  int64_t* d_ul = dev_copy(std::vector<int64_t>(U, o.user_ul));
-  int64_t* d_dl = dev_copy(std::vector<int64_t>(U, o.user_dl));
-  fognet_signal_vectors vec{(int64_t)cap, dev_alloc<int64_t>(V + 1), dev_alloc<int64_t>(cap), dev_alloc<int64_t>(cap),
-                            dev_alloc<int32_t>(cap)};
-  int64_t* d_un = dev_alloc<int64_t>(1);
+  const size_t V = N + 1 + 3 * (size_t)U, cap = 6 * (size_t)din.T;
+  DeviceMem mem;
+  int32_t* d_user_of = mem.copy(us.user_of);
+  int64_t* d_ul = mem.copy(std::vector<int64_t>(U, o.user_ul));
+  int64_t* d_dl = mem.copy(std::vector<int64_t>(U, o.user_dl));
+  fognet_signal_vectors vec{(int64_t)cap, mem.alloc<int64_t>(V + 1), mem.alloc<int64_t>(cap), mem.alloc<int64_t>(cap),
+                            mem.alloc<int32_t>(cap)};
+  int64_t* d_un = mem.alloc<int64_t>(1);
+  mem.must();
   check_ctx(ctx, fognet_signal_vectors_dev(ctx, &din, &dout, d_user_of, U, 0, d_ul, d_dl, 0, 1, &vec, d_un, nullptr),
             "fognet_signal_vectors_dev");
   std::vector<int64_t> offset(V + 1), time(cap), value(cap);
   int64_t un = 0;
-  hip_check(hipMemcpy(offset.data(), vec.offset, (V + 1) * sizeof(int64_t), hipMemcpyDeviceToHost), "hipMemcpy");
-  hip_check(hipMemcpy(time.data(), vec.time, cap * sizeof(int64_t), hipMemcpyDeviceToHost), "hipMemcpy");
-  hip_check(hipMemcpy(value.data(), vec.value, cap * sizeof(int64_t), hipMemcpyDeviceToHost), "hipMemcpy");
-  hip_check(hipMemcpy(&un, d_un, sizeof un, hipMemcpyDeviceToHost), "hipMemcpy");
-  const void* bufs[] = {din.arrive_tick, din.req_mips, din.mips, din.dl_tick, din.ul_tick, din.init_adv_tick, dout.node,
-                        dout.status, dout.start_tick, dout.done_tick, dout.stats, d_user_of, d_ul, d_dl, vec.offset,
-                        vec.time, vec.value, vec.task, d_un};
-  for (const void* b : bufs) (void)hipFree(const_cast<void*>(b));
+  mem.fetch(offset.data(), vec.offset, V + 1), mem.fetch(time.data(), vec.time, cap);
+  mem.fetch(value.data(), vec.value, cap), mem.fetch(&un, d_un, 1);
+  mem.must();
   if (un != 0) die("--vec-users: replication 0 has " + std::to_string(un) + " publishes of no known user");
   std::vector<const char*> names(U);
   for (int32_t u = 0; u < U; ++u) names[u] = us.modules[u].c_str();
   // after fognet_write_vec's ids: 0 = decisions, 1 + j = node j's queueTime
-  check(fognet_write_vec_users(o.vec.c_str(), run_id.c_str(), network.c_str(), U, in.N + 1, offset.data() + N, time.data(),
+  check(fognet_write_vec_users(o.vec.c_str(), run_id.c_str(), network.c_str(), U, din.N + 1, offset.data() + N, time.data(),
                                value.data(), names.data(), 1),
         "vec users");
 }
@@ -818,41 +849,6 @@ std::vector<int32_t> make_assignment(const Options& o, const fognet_batch_in& in
       a[(size_t)r * in.T + i] = (int32_t)((o.assign == 1 ? (uint64_t)i : (uint64_t)gen()) % N);
   }
   return a;
-}
-
-// --assign: fognet_run_assigned_dev over device copies of the host batch; the outputs come back to `out`
-int run_assigned_host(fognet_ctx* ctx, const fognet_batch_in& in, const std::vector<int32_t>& assign,
-                      const fognet_batch_out& out) {
-  const size_t R = (size_t)in.R, RT = R * (size_t)in.T, N = (size_t)in.N, NRN = (in.node_stride ? R : 1) * N;
-  auto up = [](const auto* h, size_t n) {
-    return dev_copy(std::vector<std::remove_cv_t<std::remove_pointer_t<decltype(h)>>>(h, h + n));
-  };
-  fognet_batch_in din = in;
-  din.arrive_tick = up(in.arrive_tick, RT), din.req_mips = up(in.req_mips, RT), din.mips = up(in.mips, NRN);
-  din.dl_tick = up(in.dl_tick, NRN), din.ul_tick = up(in.ul_tick, NRN), din.init_adv_tick = up(in.init_adv_tick, NRN);
-  if (in.p_busy_w) din.p_busy_w = up(in.p_busy_w, NRN), din.p_idle_w = up(in.p_idle_w, NRN);
-  int32_t* d_assign = dev_copy(assign);
-  fognet_batch_out dout{dev_alloc<int32_t>(RT), dev_alloc<uint8_t>(RT), dev_alloc<int64_t>(RT), dev_alloc<int64_t>(RT),
-                        dev_alloc<fognet_rep_stats>(R), nullptr,
-                        dev_copy(std::vector<int64_t>(out.hist, out.hist + FOGNET_HIST_METRICS * FOGNET_HIST_BINS))};
-  const int rc = fognet_run_assigned_dev(ctx, &din, d_assign, &dout, nullptr);
-  if (rc == FOGNET_OK) {
-    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    auto down = [](void* h, const void* d, size_t bytes) {
-      if (bytes) hip_check(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost), "hipMemcpy");
-    };
-    down(out.node, dout.node, RT * 4), down(out.status, dout.status, RT), down(out.start_tick, dout.start_tick, RT * 8);
-    down(out.done_tick, dout.done_tick, RT * 8), down(out.stats, dout.stats, R * sizeof(fognet_rep_stats));
-    down(out.hist, dout.hist, FOGNET_HIST_METRICS * FOGNET_HIST_BINS * sizeof(int64_t));
-  }
-  for (const void* p : {(const void*)din.arrive_tick, (const void*)din.req_mips, (const void*)din.mips,
-                        (const void*)din.dl_tick, (const void*)din.ul_tick, (const void*)din.init_adv_tick,
-                        (const void*)(in.p_busy_w ? din.p_busy_w : nullptr), (const void*)(in.p_busy_w ? din.p_idle_w : nullptr),
-                        (const void*)d_assign, (const void*)dout.node, (const void*)dout.status,
-                        (const void*)dout.start_tick, (const void*)dout.done_tick, (const void*)dout.stats,
-                        (const void*)dout.hist})
-    if (p) (void)hipFree(const_cast<void*>(p));
-  return rc;
 }
 
 // --assign: names the rule among the run attributes of a result file the library wrote
@@ -875,51 +871,56 @@ void add_run_attr(const std::string& path, const std::string& name, const std::s
   if (!w) die("cannot write " + path);
 }
 
+// BrokerBaseApp3 + ComputeBrokerApp3 (the batch engine; device entry points over one device copy of the batch).
 int run_v3(const Options& o, fognet_batch_in in, const std::string& network, const std::string& run_id,
            const UserSide* us = nullptr, int r0 = 0) {
   const size_t RT = (size_t)in.R * (size_t)in.T;
   std::vector<int32_t> node(RT);
   std::vector<uint8_t> status(RT);
-  std::vector<int64_t> start(RT), done(RT), hist((size_t)FOGNET_HIST_METRICS * FOGNET_HIST_BINS, 0);
+  std::vector<int64_t> start(RT), done(RT), hist(kHistLen, 0);
   std::vector<fognet_rep_stats> stats(in.R);
   fognet_batch_out out{node.data(), status.data(), start.data(), done.data(), stats.data(), nullptr, hist.data()};
-  // status -1: "not replayed"; fognet_run_batch fails before any replay
-  // (invalid batch, device error) or reports the first failed replication
+  // status -1: "not replayed"; the entry point fails before any replay (invalid batch, device error),
+  // a failed replication says so in its record
   for (fognet_rep_stats& s : stats) s.status = -1;
+  std::unique_ptr<fognet_ctx, void (*)(fognet_ctx*)> ctx_owner(nullptr, fognet_destroy);
+  std::optional<DeviceBatch> db;  // after the context: freed before the context goes
   fognet_ctx* ctx = nullptr;
   std::string local_err;
   if (fognet_create(&ctx, o.device) != FOGNET_OK) {
     local_err = "fognet_create: no gfx950 device " + std::to_string(o.device);
     ctx = nullptr;
   } else {
-    const int rc = o.assign ? run_assigned_host(ctx, in, make_assignment(o, in, r0), out) : fognet_run_batch(ctx, &in, &out);
-    bool replayed = true;
-    for (const fognet_rep_stats& s : stats) replayed = replayed && s.status != -1;
-    if (rc != FOGNET_OK && !replayed)
-      local_err = std::string(o.assign ? "fognet_run_assigned_dev: " : "fognet_run_batch: ") + fognet_status_string(rc) +
-                  ": " + fognet_last_error(ctx);
+    ctx_owner.reset(ctx);
+    db.emplace(in, out);
+    const int32_t* d_assign = o.assign ? db->copy(make_assignment(o, in, r0)) : nullptr;
+    if (db->err().empty()) {
+      const int rc = o.assign ? fognet_run_assigned_dev(ctx, &db->din, d_assign, &db->dout, nullptr)
+                              : fognet_run_batch_dev(ctx, &db->din, &db->dout, nullptr);
+      if (rc == FOGNET_OK) db->download(out);
+      bool replayed = true;
+      for (const fognet_rep_stats& s : stats) replayed = replayed && s.status != -1;
+      if (rc != FOGNET_OK && !replayed)
+        local_err = std::string(o.assign ? "fognet_run_assigned_dev: " : "fognet_run_batch_dev: ") +
+                    fognet_status_string(rc) + ": " + fognet_last_error(ctx);
+    }
+    if (local_err.empty() && !db->err().empty()) local_err = "device batch: " + db->err();
   }
   if (o.comm_id.empty() && !local_err.empty()) die(local_err);
   if (!o.comm_id.empty()) {  // a failed rank reports instead of dying: no rank may be left in RCCL
     if (!local_err.empty()) std::fprintf(stderr, "fognet_replay: rank %d: %s\n", o.rank, local_err.c_str());
-    if (!ranks_ready(o, local_err.empty())) {
-      if (ctx) fognet_destroy(ctx);
-      return 1;
-    }
+    if (!ranks_ready(o, local_err.empty())) return 1;
   }
   fognet_job_stats job;
   fognet_job_stats_init(&job);
   for (const fognet_rep_stats& s : stats) fognet_job_stats_add_rep(&job, &s);
   const int64_t local_failed = job.n_failed;
   if (!o.comm_id.empty()) exchange_stats(o, ctx, &job, hist);  // job + histogram of every rank
-  if (o.rank != 0) {  // rank 0 writes the results
-    fognet_destroy(ctx);
-    return local_failed ? 1 : 0;
-  }
+  if (o.rank != 0) return local_failed ? 1 : 0;               // rank 0 writes the results
   if (!o.sca.empty()) check(fognet_write_sca(o.sca.c_str(), run_id.c_str(), network.c_str(), &job, hist.data()), "sca");
   if (!o.sca.empty() && o.assign) add_run_attr(o.sca, "assign", assign_name(o));
-  if (!o.sca.empty() && o.node_stats) append_node_stats(o, ctx, in, out, network, run_id);
-  if (!o.sca.empty() && o.user_stats && us) append_user_stats(o, ctx, in, out, *us, network, run_id);
+  if (!o.sca.empty() && o.node_stats) append_node_stats(o, ctx, *db, network, run_id);
+  if (!o.sca.empty() && o.user_stats && us) append_user_stats(o, ctx, *db, *us, network, run_id);
   if (!o.vec.empty()) {  // replication 0's vectors (a failed replication has no complete outputs)
     if (stats[0].status != FOGNET_OK)
       die(std::string("--vec: replication 0 failed: ") + fognet_status_string(stats[0].status));
@@ -927,7 +928,7 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
                            node.data(), status.data(), start.data(), nullptr),
           "vec");
     if (o.assign) add_run_attr(o.vec, "assign", assign_name(o));
-    if (o.vec_users && us) append_user_vectors(o, ctx, in, out, *us, network, run_id);
+    if (o.vec_users && us) append_user_vectors(o, ctx, *db, *us, network, run_id);
   }
   if (!o.quiet) {
     std::printf("policy=%s R=%d T=%d N=%d decisions=%" PRId64 " queued=%" PRId64 " started=%" PRId64
@@ -947,7 +948,6 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
       if (stats[r].status != FOGNET_OK)
         std::printf("replication %d: %s\n", r, fognet_status_string(stats[r].status));
   }
-  fognet_destroy(ctx);
   return job.n_failed ? 1 : 0;
 }
 
@@ -957,34 +957,35 @@ int run_v2(const Options& o, const Scenario& sc, int32_t T, const std::vector<in
            const std::vector<int64_t>& first_adv, const std::string& run_id) {
   const int32_t R = o.reps, N = (int32_t)sc.mips.size();
   if (N > FOGNET_V2_MAX_NODES) die("BrokerBaseApp2 replays take at most 16384 fog nodes");
-  hip_check(hipSetDevice(o.device), "hipSetDevice");
+  if (const hipError_t e = hipSetDevice(o.device)) die(std::string("hipSetDevice: ") + hipGetErrorString(e));
   fognet_ctx* ctx = nullptr;
   if (fognet_create(&ctx, o.device) != FOGNET_OK) die("fognet_create: no gfx950 device " + std::to_string(o.device));
+  const std::unique_ptr<fognet_ctx, void (*)(fognet_ctx*)> ctx_owner(ctx, fognet_destroy);
+  DeviceMem mem;  // after the context: freed before the context goes
   std::vector<int32_t> bm(R, sc.broker_mips);
   std::vector<double> rt(R, 0.01);  // MqttMsgPublish.requiredTime (mqttApp2.cc:372)
   std::vector<int64_t> stop(R, sc.stop);
   fognet_v2_in in{};
-  in.R = R;
-  in.T = T;
-  in.N = N;
-  in.arrive_tick = dev_copy(arrive);
-  in.req_mips = dev_copy(req);
-  in.broker_mips = dev_copy(bm);
-  in.required_time_s = dev_copy(rt);
-  in.stop_tick = dev_copy(stop);
-  in.mips = dev_copy(sc.mips);
-  in.dl_tick = dev_copy(dl);
-  in.ul_tick = dev_copy(ul);
-  in.first_adv_tick = dev_copy(first_adv);
+  in.R = R, in.T = T, in.N = N;
+  in.arrive_tick = mem.copy(arrive);
+  in.req_mips = mem.copy(req);
+  in.broker_mips = mem.copy(bm);
+  in.required_time_s = mem.copy(rt);
+  in.stop_tick = mem.copy(stop);
+  in.mips = mem.copy(sc.mips);
+  in.dl_tick = mem.copy(dl);
+  in.ul_tick = mem.copy(ul);
+  in.first_adv_tick = mem.copy(first_adv);
   const size_t RT = (size_t)R * T;
-  fognet_v2_out out{dev_alloc<int32_t>(RT), dev_alloc<uint8_t>(RT), dev_alloc<int64_t>(RT), dev_alloc<int64_t>(RT),
-                    dev_alloc<fognet_v2_stats>(R)};
+  fognet_v2_out out{mem.alloc<int32_t>(RT), mem.alloc<uint8_t>(RT), mem.alloc<int64_t>(RT), mem.alloc<int64_t>(RT),
+                    mem.alloc<fognet_v2_stats>(R)};
+  mem.must();
   check_ctx(ctx, fognet_run_v2_dev(ctx, &in, &out, nullptr), "fognet_run_v2_dev");
-  hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
   std::vector<fognet_v2_stats> st(R);
   std::vector<int32_t> node(RT);
-  hip_check(hipMemcpy(st.data(), out.stats, R * sizeof(fognet_v2_stats), hipMemcpyDeviceToHost), "hipMemcpy");
-  hip_check(hipMemcpy(node.data(), out.node, RT * sizeof(int32_t), hipMemcpyDeviceToHost), "hipMemcpy");
+  mem.sync();
+  mem.fetch(st.data(), out.stats, (size_t)R), mem.fetch(node.data(), out.node, RT);
+  mem.must();
   fognet_v2_stats tot{};
   int failed = 0;
   for (const fognet_v2_stats& s : st) {
@@ -1023,13 +1024,6 @@ int run_v2(const Options& o, const Scenario& sc, int32_t T, const std::vector<in
     for (int k = 0; k < N; ++k) std::printf("%s%" PRId64, k ? "," : "", per[k]);
     std::printf("\n");
   }
-  for (const void* p : {(const void*)in.arrive_tick, (const void*)in.req_mips, (const void*)in.broker_mips,
-                        (const void*)in.required_time_s, (const void*)in.stop_tick, (const void*)in.mips,
-                        (const void*)in.dl_tick, (const void*)in.ul_tick, (const void*)in.first_adv_tick,
-                        (const void*)out.node, (const void*)out.status, (const void*)out.start_tick,
-                        (const void*)out.done_tick, (const void*)out.stats})
-    (void)hipFree(const_cast<void*>(p));
-  fognet_destroy(ctx);
   return failed ? 1 : 0;
 }
 

@@ -41,8 +41,9 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def _stream_ptr(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+def _stream_ptr(device, stream=None) -> C.c_void_p:
+    """The caller's torch stream, else the device's current one."""
+    return C.c_void_p((stream if stream is not None else torch.cuda.current_stream(device)).cuda_stream)
 
 
 def _check_out(out, m: int, device):
@@ -59,6 +60,92 @@ def _check_bytes(t, nbytes: int, device, what: str):
     if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < nbytes or t.device != device or not t.is_contiguous():
         raise FognetError(_abi.FOGNET_ERR_ARG, f"{what}: a contiguous uint8 tensor of at least {nbytes} B on {device}")
     return t
+
+
+# ---- one marshalling of a trace and of a replay's outputs (they read shapes and data_ptr() only) ----
+
+def _dims(trace: dict):
+    """R, T, N and the node stride of a trace: N for per-replication node parameters [R, N], 0 for shared [N]."""
+    R, T = trace["arrive"].shape
+    mips = trace["mips"]
+    N = mips.shape[-1]
+    return R, T, N, (N if mips.dim() == 2 else 0)
+
+
+def _check_node_params(trace: dict, keys):
+    """Every node-parameter array has the shape of mips: the kernels index them all with its stride."""
+    mips = trace["mips"]
+    for k in keys:
+        if tuple(trace[k].shape) != tuple(mips.shape):
+            raise FognetError(_abi.FOGNET_ERR_ARG, f"{k} has shape {tuple(trace[k].shape)}, mips {tuple(mips.shape)}")
+
+
+def _check_trace_shapes(trace: dict, R: int, T: int):
+    """The host-side shape checks of a replay (run_batch, run_assigned); the passes over its outputs make none."""
+    power = ("p_busy", "p_idle") if trace.get("p_busy") is not None else ()
+    _check_node_params(trace, ("dl", "ul", "init") + power + (("down",) if trace.get("down") is not None else ()))
+    mips = trace["mips"]
+    if tuple(trace["req"].shape) != (R, T) or (mips.dim() == 2 and mips.shape[0] != R):
+        raise FognetError(_abi.FOGNET_ERR_ARG, "trace arrays disagree on R/T")
+
+
+def _batch_in(trace: dict, R, T, N, stride, policy, *, ring_capacity=0, power=False, down=False, region=False,
+              hier_up_tick=0, hier_threshold_s=0, flags=0) -> _abi.BatchIn:
+    """fognet_batch_in of a trace; ``power`` / ``down`` / ``region``: forward these optional arrays if it has them."""
+    opt = lambda on, k: _ptr(trace.get(k)) if on else None  # noqa: E731
+    return _abi.BatchIn(
+        R=R, T=T, N=N, policy=policy, node_stride=stride, ring_capacity=ring_capacity,
+        arrive_tick=_ptr(trace["arrive"]), req_mips=_ptr(trace["req"]), mips=_ptr(trace["mips"]),
+        dl_tick=_ptr(trace["dl"]), ul_tick=_ptr(trace["ul"]), init_adv_tick=_ptr(trace["init"]),
+        p_busy_w=opt(power, "p_busy"), p_idle_w=opt(power, "p_idle"), down_tick=opt(down, "down"),
+        region=opt(region, "region"), hier_up_tick=hier_up_tick, hier_threshold_s=hier_threshold_s, flags=flags)
+
+
+def _batch_out(out, *, energy=False, hist=False, escalated=False) -> _abi.BatchOut:
+    """fognet_batch_out of a BatchResult: the per-task arrays and the records, and what the flags add."""
+    return _abi.BatchOut(
+        node=_ptr(out.node), status=_ptr(out.status), start_tick=_ptr(out.start_tick), done_tick=_ptr(out.done_tick),
+        stats=_ptr(out.stats), node_energy_j=_ptr(out.node_energy) if energy else None,
+        hist=_ptr(out.hist) if hist else None, escalated=_ptr(out.escalated) if escalated else None)
+
+
+def _policy_of(out, policy) -> int:
+    """The ABI value of a policy name or number; None: what the replay recorded on ``out`` (REF_V3 if nothing)."""
+    if policy is None:
+        policy = out.policy if out.policy is not None else _abi.FOGNET_POLICY_REF_V3
+    return POLICIES[policy] if isinstance(policy, str) else int(policy)
+
+
+def _record_buffer(res, nbytes: int, dev, what: str, zero: bool = False, alloc: int | None = None):
+    """The caller's record buffer, checked, else a new one of ``alloc`` (default ``nbytes``) bytes."""
+    if res is not None:
+        return _check_bytes(res, nbytes, dev, what)
+    return (torch.zeros if zero else torch.empty)(nbytes if alloc is None else alloc, dtype=torch.uint8, device=dev)
+
+
+def _to_dev(x, dtype, dev) -> torch.Tensor:
+    """A host array or tensor as a contiguous tensor of ``dtype`` on ``dev``."""
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    return t.to(device=dev, dtype=dtype).contiguous()
+
+
+def _user_tables(user_of, user_ul, user_dl, R: int, T: int, dev):
+    """(user_of int32 [R, T], ul, dl int64 [U] or [R, U], U, link stride) of a pass keyed by user."""
+    uo = _to_dev(user_of, torch.int32, dev)
+    uu, ud = _to_dev(user_ul, torch.int64, dev), _to_dev(user_dl, torch.int64, dev)
+    if tuple(uo.shape) != (R, T):
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"user_of must have shape [R, T], got {tuple(uo.shape)}")
+    U = uu.shape[-1] if uu.dim() else -1
+    if uu.shape != ud.shape or tuple(uu.shape) not in ((U,), (R, U)):
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"user links must both have shape [U] or [R, U], got "
+                                               f"{tuple(uu.shape)} / {tuple(ud.shape)}")
+    return uo, uu, ud, U, (U if uu.dim() == 2 else 0)
+
+
+def _raise_unassigned(what: str, bad: int, U: int):
+    if bad:
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"{what}: {bad} decided publishes name a user outside "
+                                               f"[0, {U}) (allow_unassigned=True leaves them out)")
 
 
 class Context:
@@ -296,42 +383,29 @@ def run_batch(ctx: Context, trace: dict, out: BatchResult | None = None, ring_ca
     parent broker took the decision under EXT_HIER, all 0 under the other
     policies); an ``out`` that carries the array gets it filled either way.
     """
-    arrive, req = trace["arrive"], trace["req"]
-    R, T = arrive.shape
-    mips = trace["mips"]
-    N = mips.shape[-1]
-    stride = N if mips.dim() == 2 else 0
-    pol = POLICIES[policy] if isinstance(policy, str) else int(policy)
-    energy = trace.get("p_busy") is not None
-    # host-side shape checks: the kernels index every array with these strides
-    down = trace.get("down")
-    for k in ("dl", "ul", "init") + (("p_busy", "p_idle") if energy else ()) + (("down",) if down is not None else ()):
-        if tuple(trace[k].shape) != tuple(mips.shape):
-            raise FognetError(_abi.FOGNET_ERR_ARG, f"{k} has shape {tuple(trace[k].shape)}, mips {tuple(mips.shape)}")
-    if tuple(req.shape) != (R, T) or (mips.dim() == 2 and mips.shape[0] != R):
-        raise FognetError(_abi.FOGNET_ERR_ARG, "trace arrays disagree on R/T")
+    dims = R, T, N, _ = _dims(trace)
+    dev = trace["arrive"].device
+    pol = _policy_of(None, policy)
+    _check_trace_shapes(trace, R, T)
     if out is not None and ((out.node is not None and tuple(out.node.shape) != (R, T))
                             or out.stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize):
         raise FognetError(_abi.FOGNET_ERR_ARG, "output buffers too small for the trace")
     if out is None:
-        out = allocate_outputs(R, T, arrive.device, N=N, energy=energy, hist=hist, escalated=escalated)
+        out = allocate_outputs(R, T, dev, N=N, energy=trace.get("p_busy") is not None, hist=hist, escalated=escalated)
     if out.escalated is not None and (out.escalated.dtype != torch.uint8 or tuple(out.escalated.shape) != (R, T)
                                       or out.escalated.stride(-1) != 1 or (R > 1 and out.escalated.stride(0) != T)):
         raise FognetError(_abi.FOGNET_ERR_ARG, f"out.escalated: a row-contiguous uint8 [{R}, {T}] tensor")
     region = trace.get("region")
     if pol == _abi.FOGNET_POLICY_EXT_HIER and (region is None or tuple(region.shape) != (R, T)):
         raise FognetError(_abi.FOGNET_ERR_ARG, "EXT_HIER needs trace['region'] of shape [R, T]")
-    bi = _abi.BatchIn(R, T, N, pol, stride, ring_capacity,
-                      _ptr(arrive), _ptr(req), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
-                      _ptr(trace["init"]), _ptr(trace.get("p_busy")), _ptr(trace.get("p_idle")), _ptr(down),
-                      _ptr(region), int(hier_up_tick), int(hier_threshold_s),
-                      _abi.FLAG_REF_ABORT if ref_abort else 0)
-    bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick),
-                       _ptr(out.stats), _ptr(out.node_energy), _ptr(out.hist), _ptr(out.escalated))
-    s = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr(arrive.device)
+    # every array the trace and the outputs have; region, hop and threshold as given
+    bi = _batch_in(trace, *dims, pol, ring_capacity=ring_capacity, power=True, down=True, region=True,
+                   hier_up_tick=int(hier_up_tick), hier_threshold_s=int(hier_threshold_s),
+                   flags=_abi.FLAG_REF_ABORT if ref_abort else 0)
+    bo = _batch_out(out, energy=True, hist=True, escalated=True)
     fn = {"all": ctx._lib.fognet_run_batch_dev, "replay": ctx._lib.fognet_replay_dev,
           "stats": ctx._lib.fognet_rep_stats_dev}[stage]
-    ctx.check(fn(ctx.handle, C.byref(bi), C.byref(bo), s), f"run_batch[{stage}]")
+    ctx.check(fn(ctx.handle, C.byref(bi), C.byref(bo), _stream_ptr(dev, stream)), f"run_batch[{stage}]")
     out.policy = pol  # what user_stats goes by when it is given no policy
     out.hier_up_tick = int(hier_up_tick) if pol == _abi.FOGNET_POLICY_EXT_HIER else 0
     return out
@@ -352,36 +426,22 @@ def run_assigned(ctx: Context, trace: dict, assign: torch.Tensor, out: BatchResu
     The result serves :func:`node_stats`, :func:`per_user_stats`, :func:`user_stats` and
     :func:`signal_vectors` as a REF_V3 replay's does.  A replication with a bad input (an
     ``assign`` entry outside [0, N) among them) has status FOGNET_ERR_ARG in its record."""
-    arrive, req = trace["arrive"], trace["req"]
-    R, T = arrive.shape
-    mips = trace["mips"]
-    N = mips.shape[-1]
-    stride = N if mips.dim() == 2 else 0
-    power = trace.get("p_busy") is not None
-    down = trace.get("down")
-    for k in ("dl", "ul", "init") + (("p_busy", "p_idle") if power else ()) + (("down",) if down is not None else ()):
-        if tuple(trace[k].shape) != tuple(mips.shape):
-            raise FognetError(_abi.FOGNET_ERR_ARG, f"{k} has shape {tuple(trace[k].shape)}, mips {tuple(mips.shape)}")
-    if tuple(req.shape) != (R, T) or (mips.dim() == 2 and mips.shape[0] != R):
-        raise FognetError(_abi.FOGNET_ERR_ARG, "trace arrays disagree on R/T")
+    dims = R, T, N, _ = _dims(trace)
+    dev = trace["arrive"].device
+    _check_trace_shapes(trace, R, T)
     if (not isinstance(assign, torch.Tensor) or assign.dtype != torch.int32 or tuple(assign.shape) != (R, T)
-            or assign.device != arrive.device or not assign.is_contiguous()):
-        raise FognetError(_abi.FOGNET_ERR_ARG, f"assign: a contiguous int32 [{R}, {T}] tensor on {arrive.device}")
-    if energy and not power:
+            or assign.device != dev or not assign.is_contiguous()):
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"assign: a contiguous int32 [{R}, {T}] tensor on {dev}")
+    if energy and trace.get("p_busy") is None:
         raise FognetError(_abi.FOGNET_ERR_ARG, "energy needs the power model (p_busy / p_idle) in the trace")
     if out is None:
-        out = allocate_outputs(R, T, arrive.device, N=N, energy=energy, hist=hist)
+        out = allocate_outputs(R, T, dev, N=N, energy=energy, hist=hist)
     if out.node is None or tuple(out.node.shape) != (R, T) or out.stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
         raise FognetError(_abi.FOGNET_ERR_ARG, "run_assigned needs the per-task output arrays [R, T] and R records")
-    bi = _abi.BatchIn(R, T, N, _abi.FOGNET_POLICY_REF_V3, stride, 0,
-                      _ptr(arrive), _ptr(req), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
-                      _ptr(trace["init"]), _ptr(trace.get("p_busy")), _ptr(trace.get("p_idle")), _ptr(down),
-                      None, 0, 0, 0)
-    bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick),
-                       _ptr(out.stats), _ptr(out.node_energy), _ptr(out.hist), _ptr(out.escalated))
-    s = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr(arrive.device)
+    bi = _batch_in(trace, *dims, _abi.FOGNET_POLICY_REF_V3, power=True, down=True)  # no region, hop or flags
+    bo = _batch_out(out, energy=True, hist=True, escalated=True)
     fn = ctx._lib.fognet_run_assigned_dev if stats else ctx._lib.fognet_replay_assigned_dev
-    ctx.check(fn(ctx.handle, C.byref(bi), _ptr(assign), C.byref(bo), s), "run_assigned")
+    ctx.check(fn(ctx.handle, C.byref(bi), _ptr(assign), C.byref(bo), _stream_ptr(dev, stream)), "run_assigned")
     out.policy = _abi.FOGNET_POLICY_REF_V3  # what the passes over the outputs go by
     out.hier_up_tick = 0
     return out
@@ -429,15 +489,16 @@ def run_generated(ctx: Context, seed: int, R: int, T: int, N: int, mean_gap_tick
         out = allocate_outputs(R, T, device, N=N, energy=energy and pb is not None, hist=hist, per_task=False)
     elif out.stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
         raise FognetError(_abi.FOGNET_ERR_ARG, "stats buffer too small")
-    pol = POLICIES[policy] if isinstance(policy, str) else int(policy)
+    pol = _policy_of(None, policy)
     gp = _abi.GenParams(seed & 0xFFFFFFFF, req_lo, req_hi, 0, _ptr(mg), _ptr(ls))
     hier = pol == _abi.FOGNET_POLICY_EXT_HIER
-    bi = _abi.BatchIn(R, T, N, pol, stride, ring_capacity, None, None, None, None, None, None,
-                      _ptr(pb), _ptr(pi), None, None, hier_up_tick if hier else 0, hier_threshold_s if hier else 0, 0)
-    bo = _abi.BatchOut(None, None, None, None, _ptr(out.stats), _ptr(out.node_energy), _ptr(out.hist))
-    s = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr(device)
-    ctx.check(ctx._lib.fognet_run_generated_dev(ctx.handle, C.byref(gp), r0, C.byref(bi), C.byref(bo), s),
-              "run_generated")
+    # stated apart from _batch_in / _batch_out: no trace in memory and no per-task output
+    bi = _abi.BatchIn(R=R, T=T, N=N, policy=pol, node_stride=stride, ring_capacity=ring_capacity,
+                      p_busy_w=_ptr(pb), p_idle_w=_ptr(pi), hier_up_tick=hier_up_tick if hier else 0,
+                      hier_threshold_s=hier_threshold_s if hier else 0)
+    bo = _abi.BatchOut(stats=_ptr(out.stats), node_energy_j=_ptr(out.node_energy), hist=_ptr(out.hist))
+    ctx.check(ctx._lib.fognet_run_generated_dev(ctx.handle, C.byref(gp), r0, C.byref(bi), C.byref(bo),
+                                                _stream_ptr(device, stream)), "run_generated")
     out._keep = (mg, ls)
     return out
 
@@ -445,6 +506,14 @@ def run_generated(ctx: Context, seed: int, R: int, T: int, N: int, mean_gap_tick
 def _hier_up(out: BatchResult, hier_up_tick) -> int:
     """The EXT_HIER hop a statistics pass adds to escalated tasks: the caller's, else the replay's."""
     return int(out.hier_up_tick if hier_up_tick is None else hier_up_tick)
+
+
+def _pass_descriptors(trace, out, dims, pol, hier_up_tick, down=False):
+    """What user_stats, per_user_stats and node_stats (``down``: node_stats alone) hand their kernels: no power
+    model, no energy rows, no histogram; region, the escalation flags and the hop only under EXT_HIER."""
+    hier = pol == _abi.FOGNET_POLICY_EXT_HIER
+    hop = _hier_up(out, hier_up_tick) if hier else 0
+    return _batch_in(trace, *dims, pol, down=down, region=hier, hier_up_tick=hop), _batch_out(out, escalated=hier)
 
 
 def user_stats(ctx: Context, trace: dict, out: BatchResult, user_ul, user_dl,
@@ -466,35 +535,17 @@ def user_stats(ctx: Context, trace: dict, out: BatchResult, user_ul, user_dl,
     were escalated.  A failed
     replication (status other than FOGNET_OK / FOGNET_REF_ABORTED) gets the
     empty record."""
-    arrive = trace["arrive"]
-    R, T = arrive.shape
-    dev = arrive.device
-    uu = torch.as_tensor(np.asarray(user_ul) if not isinstance(user_ul, torch.Tensor) else user_ul,
-                         dtype=torch.int64).to(dev).contiguous()
-    ud = torch.as_tensor(np.asarray(user_dl) if not isinstance(user_dl, torch.Tensor) else user_dl,
-                         dtype=torch.int64).to(dev).contiguous()
+    dims = R, T, _, _ = _dims(trace)
+    dev = trace["arrive"].device
+    uu, ud = _to_dev(user_ul, torch.int64, dev), _to_dev(user_dl, torch.int64, dev)
     per_task = 1 if uu.dim() == 2 else 0
     want = (R, T) if per_task else (R,)
     if tuple(uu.shape) != want or tuple(ud.shape) != want:
         raise FognetError(_abi.FOGNET_ERR_ARG, f"user links must both have shape [R] or [R, T], got "
                                                f"{tuple(uu.shape)} / {tuple(ud.shape)}")
-    mips = trace["mips"]
-    N = mips.shape[-1]
     nres = R * _abi.USER_STATS_DTYPE.itemsize
-    if res is None:
-        res = torch.zeros(nres, dtype=torch.uint8, device=dev)
-    else:
-        _check_bytes(res, nres, dev, "res")
-    if policy is None:
-        policy = out.policy if out.policy is not None else _abi.FOGNET_POLICY_REF_V3
-    pol = POLICIES[policy] if isinstance(policy, str) else int(policy)
-    hier = pol == _abi.FOGNET_POLICY_EXT_HIER
-    bi = _abi.BatchIn(R, T, N, pol, N if mips.dim() == 2 else 0, 0,
-                      _ptr(arrive), _ptr(trace["req"]), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
-                      _ptr(trace["init"]), None, None, None, _ptr(trace.get("region")) if hier else None,
-                      _hier_up(out, hier_up_tick) if hier else 0)
-    bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick),
-                       _ptr(out.stats), None, None, _ptr(out.escalated) if hier else None)
+    res = _record_buffer(res, nres, dev, "res", zero=True)
+    bi, bo = _pass_descriptors(trace, out, dims, _policy_of(out, policy), hier_up_tick)
     ctx.check(ctx._lib.fognet_user_stats_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(uu), _ptr(ud), per_task,
                                              _ptr(res), _stream_ptr(dev)), "user_stats")
     return res[:nres].cpu().numpy().view(_abi.USER_STATS_DTYPE)
@@ -511,24 +562,11 @@ def node_stats(ctx: Context, trace: dict, out: BatchResult, policy: str | int = 
     escalation flags, ``run_batch(..., escalated=True)`` -- an escalated task is
     enqueued ``hier_up_tick`` later (None: the hop run_batch recorded on ``out``) --
     and refused without them, FOGNET_ERR_UNSUPPORTED)."""
-    arrive = trace["arrive"]
-    R, T = arrive.shape
-    dev = arrive.device
-    mips = trace["mips"]
-    N = mips.shape[-1]
+    dims = R, _, N, _ = _dims(trace)
+    dev = trace["arrive"].device
     nres = R * N * _abi.NODE_STATS_DTYPE.itemsize
-    if res is None:
-        res = torch.empty(nres, dtype=torch.uint8, device=dev)
-    else:
-        _check_bytes(res, nres, dev, "res")
-    pol = POLICIES[policy] if isinstance(policy, str) else int(policy)
-    hier = pol == _abi.FOGNET_POLICY_EXT_HIER
-    bi = _abi.BatchIn(R, T, N, pol, N if mips.dim() == 2 else 0, 0,
-                      _ptr(arrive), _ptr(trace["req"]), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
-                      _ptr(trace["init"]), None, None, _ptr(trace.get("down")), _ptr(trace.get("region")) if hier else None,
-                      _hier_up(out, hier_up_tick) if hier else 0)
-    bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick),
-                       _ptr(out.stats), None, None, _ptr(out.escalated) if hier else None)
+    res = _record_buffer(res, nres, dev, "res")
+    bi, bo = _pass_descriptors(trace, out, dims, _policy_of(out, policy), hier_up_tick, down=True)
     ctx.check(ctx._lib.fognet_node_stats_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(res), _stream_ptr(dev)),
               "node_stats")
     return res[:nres].view(R, N * _abi.NODE_STATS_DTYPE.itemsize)
@@ -543,10 +581,7 @@ def reduce_node_stats(ctx: Context, node_stats: torch.Tensor, stats: torch.Tenso
     ``out``: the device buffer written to (uint8, N * sizeof(fognet_node_stats))."""
     nout = N * _abi.NODE_STATS_DTYPE.itemsize
     dev = stats.device
-    if out is None:
-        out = torch.empty(max(nout, 1), dtype=torch.uint8, device=dev)
-    else:
-        _check_bytes(out, nout, dev, "out")
+    out = _record_buffer(out, nout, dev, "out", alloc=max(nout, 1))
     if node_stats.numel() < R * nout or stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
         raise FognetError(_abi.FOGNET_ERR_ARG, "node_stats / stats smaller than R replications")
     ctx.check(ctx._lib.fognet_reduce_node_stats_dev(ctx.handle, _ptr(node_stats), _ptr(stats), R, N, _ptr(out),
@@ -585,48 +620,20 @@ def per_user_stats(ctx: Context, trace: dict, out: BatchResult, user_of, user_ul
     into these buffers instead of new ones.
     ``policy`` and ``hier_up_tick``: as for :func:`user_stats` (None: what run_batch
     recorded on ``out``); EXT_HIER needs ``out.escalated`` and is refused without it."""
-    arrive = trace["arrive"]
-    R, T = arrive.shape
-    dev = arrive.device
-
-    def on_dev(x, dt):
-        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-        return t.to(device=dev, dtype=dt).contiguous()
-    uo, uu, ud = on_dev(user_of, torch.int32), on_dev(user_ul, torch.int64), on_dev(user_dl, torch.int64)
-    if tuple(uo.shape) != (R, T):
-        raise FognetError(_abi.FOGNET_ERR_ARG, f"user_of must have shape [R, T], got {tuple(uo.shape)}")
-    U = uu.shape[-1] if uu.dim() else -1
-    if uu.shape != ud.shape or tuple(uu.shape) not in ((U,), (R, U)):
-        raise FognetError(_abi.FOGNET_ERR_ARG, f"user links must both have shape [U] or [R, U], got "
-                                               f"{tuple(uu.shape)} / {tuple(ud.shape)}")
-    mips = trace["mips"]
-    N = mips.shape[-1]
+    dims = R, T, _, _ = _dims(trace)
+    dev = trace["arrive"].device
+    uo, uu, ud, U, link_stride = _user_tables(user_of, user_ul, user_dl, R, T, dev)
     nres = R * U * _abi.USER_STATS_DTYPE.itemsize
-    if res is None:
-        res = torch.empty(nres, dtype=torch.uint8, device=dev)
-    else:
-        _check_bytes(res, nres, dev, "res")
+    res = _record_buffer(res, nres, dev, "res")
     un = n_unassigned if n_unassigned is not None else torch.empty(R, dtype=torch.int64, device=dev)
     if un.dtype != torch.int64 or un.numel() != R or un.device != dev or not un.is_contiguous():
         raise FognetError(_abi.FOGNET_ERR_ARG, "n_unassigned must be a contiguous int64 [R] tensor on the trace's device")
-    if policy is None:
-        policy = out.policy if out.policy is not None else _abi.FOGNET_POLICY_REF_V3
-    pol = POLICIES[policy] if isinstance(policy, str) else int(policy)
-    hier = pol == _abi.FOGNET_POLICY_EXT_HIER
-    bi = _abi.BatchIn(R, T, N, pol, N if mips.dim() == 2 else 0, 0,
-                      _ptr(arrive), _ptr(trace["req"]), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
-                      _ptr(trace["init"]), None, None, None, _ptr(trace.get("region")) if hier else None,
-                      _hier_up(out, hier_up_tick) if hier else 0)
-    bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick),
-                       _ptr(out.stats), None, None, _ptr(out.escalated) if hier else None)
-    ctx.check(ctx._lib.fognet_per_user_stats_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(uo), U,
-                                                 U if uu.dim() == 2 else 0, _ptr(uu), _ptr(ud), _ptr(res), _ptr(un),
-                                                 _stream_ptr(dev)), "per_user_stats")
+    bi, bo = _pass_descriptors(trace, out, dims, _policy_of(out, policy), hier_up_tick)
+    ctx.check(ctx._lib.fognet_per_user_stats_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(uo), U, link_stride,
+                                                 _ptr(uu), _ptr(ud), _ptr(res), _ptr(un), _stream_ptr(dev)),
+              "per_user_stats")
     if not allow_unassigned and R > 0:
-        bad = int(un.sum().item())
-        if bad:
-            raise FognetError(_abi.FOGNET_ERR_ARG, f"per_user_stats: {bad} decided publishes name a user outside "
-                                                   f"[0, {U}) (allow_unassigned=True leaves them out)")
+        _raise_unassigned("per_user_stats", int(un.sum().item()), U)
     return res[:nres].view(R, U * _abi.USER_STATS_DTYPE.itemsize), un
 
 
@@ -647,23 +654,10 @@ def signal_vectors(ctx: Context, trace: dict, out: BatchResult, user_of, user_ul
     and returns the device tensors instead (no copy back, no check of ``n_unassigned``).  A
     non-zero ``n_unassigned`` raises FognetError (FOGNET_ERR_ARG) unless ``allow_unassigned``.  ``policy``: the replay's (None: what run_batch recorded on ``out``);
     "REF_V3" and "EXT_LAT"; "EXT_HIER" is refused (FOGNET_ERR_UNSUPPORTED, nothing written)."""
-    arrive = trace["arrive"]
-    R, T = arrive.shape
-    dev = arrive.device
+    dims = R, T, N, _ = _dims(trace)
+    dev = trace["arrive"].device
     Rv = R - r0 if Rv is None else Rv
-
-    def on_dev(x, dt):
-        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-        return t.to(device=dev, dtype=dt).contiguous()
-    uo, uu, ud = on_dev(user_of, torch.int32), on_dev(user_ul, torch.int64), on_dev(user_dl, torch.int64)
-    if tuple(uo.shape) != (R, T):
-        raise FognetError(_abi.FOGNET_ERR_ARG, f"user_of must have shape [R, T], got {tuple(uo.shape)}")
-    U = uu.shape[-1] if uu.dim() else -1
-    if uu.shape != ud.shape or tuple(uu.shape) not in ((U,), (R, U)):
-        raise FognetError(_abi.FOGNET_ERR_ARG, f"user links must both have shape [U] or [R, U], got "
-                                               f"{tuple(uu.shape)} / {tuple(ud.shape)}")
-    mips = trace["mips"]
-    N = mips.shape[-1]
+    uo, uu, ud, U, link_stride = _user_tables(user_of, user_ul, user_dl, R, T, dev)
     V, cap, rows = N + 1 + 3 * U, 6 * T, max(Rv, 0)
     shapes = dict(offset=((rows, V + 1), torch.int64), time=((rows, cap), torch.int64), value=((rows, cap), torch.int64),
                   task=((rows, cap), torch.int32), n_unassigned=((rows,), torch.int64))
@@ -675,26 +669,17 @@ def signal_vectors(ctx: Context, trace: dict, out: BatchResult, user_of, user_ul
         if t.dtype != dt or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
             raise FognetError(_abi.FOGNET_ERR_ARG, f"signal_vectors: {k} must be a contiguous {dt} tensor of shape "
                                                    f"{shape} on the trace's device")
-    if policy is None:
-        policy = out.policy if out.policy is not None else _abi.FOGNET_POLICY_REF_V3
-    pol = POLICIES[policy] if isinstance(policy, str) else int(policy)
-    bi = _abi.BatchIn(R, T, N, pol, N if mips.dim() == 2 else 0, 0,
-                      _ptr(arrive), _ptr(trace["req"]), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]),
-                      _ptr(trace["init"]), None, None, None,
-                      _ptr(trace.get("region")) if pol == _abi.FOGNET_POLICY_EXT_HIER else None)
-    bo = _abi.BatchOut(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick), _ptr(out.stats))
+    pol = _policy_of(out, policy)
+    bi, bo = _batch_in(trace, *dims, pol, region=pol == _abi.FOGNET_POLICY_EXT_HIER), _batch_out(out)  # no hop
     vec = _abi.SignalVectors(cap, _ptr(b["offset"]), _ptr(b["time"]), _ptr(b["value"]), _ptr(b["task"]))
-    ctx.check(ctx._lib.fognet_signal_vectors_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(uo), U,
-                                                 U if uu.dim() == 2 else 0, _ptr(uu), _ptr(ud), r0, Rv, C.byref(vec),
-                                                 _ptr(b["n_unassigned"]), _stream_ptr(dev)), "signal_vectors")
+    ctx.check(ctx._lib.fognet_signal_vectors_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(uo), U, link_stride,
+                                                 _ptr(uu), _ptr(ud), r0, Rv, C.byref(vec), _ptr(b["n_unassigned"]),
+                                                 _stream_ptr(dev)), "signal_vectors")
     if not to_host:
         return {k: b[k] for k in shapes}
     got = {k: b[k].cpu().numpy() for k in shapes}
     if not allow_unassigned and rows > 0:
-        bad = int(got["n_unassigned"].sum())
-        if bad:
-            raise FognetError(_abi.FOGNET_ERR_ARG, f"signal_vectors: {bad} decided publishes name a user outside "
-                                                   f"[0, {U}) (allow_unassigned=True leaves them out)")
+        _raise_unassigned("signal_vectors", int(got["n_unassigned"].sum()), U)
     return got
 
 
@@ -708,10 +693,7 @@ def reduce_user_stats(ctx: Context, user_stats: torch.Tensor, stats: torch.Tenso
     U * sizeof(fognet_user_stats))."""
     nout = U * _abi.USER_STATS_DTYPE.itemsize
     dev = stats.device
-    if out is None:
-        out = torch.empty(max(nout, 1), dtype=torch.uint8, device=dev)
-    else:
-        _check_bytes(out, nout, dev, "out")
+    out = _record_buffer(out, nout, dev, "out", alloc=max(nout, 1))
     if user_stats.numel() < R * nout or stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
         raise FognetError(_abi.FOGNET_ERR_ARG, "user_stats / stats smaller than R replications")
     ctx.check(ctx._lib.fognet_reduce_user_stats_dev(ctx.handle, _ptr(user_stats), _ptr(stats), R, U, _ptr(out),
@@ -755,14 +737,11 @@ def run_v2(ctx: Context, trace: dict, broker_mips, stop_tick, required_time_s=0.
     [N]; ``broker_mips``, ``stop_tick``, ``required_time_s``: scalars or [R]
     (host values, or device tensors [R] of the ABI dtype, used as they are).
     ``out``: write into these buffers (V2Result layout) instead of new ones."""
-    arrive, req = trace["arrive"], trace["req"]
-    R, T = arrive.shape
+    arrive, req, mips = trace["arrive"], trace["req"], trace["mips"]
+    R, T, N, stride = _dims(trace)
     dev = arrive.device
-    mips = trace["mips"]
-    N = mips.shape[-1]
-    for k in ("dl", "ul", "first_adv"):
-        if tuple(trace[k].shape) != tuple(mips.shape):
-            raise FognetError(_abi.FOGNET_ERR_ARG, f"{k} has shape {tuple(trace[k].shape)}, mips {tuple(mips.shape)}")
+    _check_node_params(trace, ("dl", "ul", "first_adv"))
+
     def per(v, dt):
         if isinstance(v, torch.Tensor):
             if v.dtype != dt or tuple(v.shape) != (R,) or v.device != dev or not v.is_contiguous():
@@ -783,11 +762,10 @@ def run_v2(ctx: Context, trace: dict, broker_mips, stop_tick, required_time_s=0.
             if t.dtype != dt or tuple(t.shape) != (R, T) or t.device != dev or not t.is_contiguous():
                 raise FognetError(_abi.FOGNET_ERR_ARG, f"out.{k}: contiguous {dt} [{R}, {T}] on {dev}")
         _check_bytes(out.stats, R * _abi.V2_STATS_DTYPE.itemsize, dev, "out.stats")
-    vi = _abi.V2In(R, T, N, N if mips.dim() == 2 else 0, queue_capacity, 0, _ptr(arrive), _ptr(req), _ptr(bm), _ptr(rt),
+    vi = _abi.V2In(R, T, N, stride, queue_capacity, 0, _ptr(arrive), _ptr(req), _ptr(bm), _ptr(rt),
                    _ptr(st_), _ptr(mips), _ptr(trace["dl"]), _ptr(trace["ul"]), _ptr(trace["first_adv"]))
     vo = _abi.V2Out(_ptr(out.node), _ptr(out.status), _ptr(out.start_tick), _ptr(out.done_tick), _ptr(out.stats))
-    s = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr(dev)
-    ctx.check(ctx._lib.fognet_run_v2_dev(ctx.handle, C.byref(vi), C.byref(vo), s), "run_v2")
+    ctx.check(ctx._lib.fognet_run_v2_dev(ctx.handle, C.byref(vi), C.byref(vo), _stream_ptr(dev, stream)), "run_v2")
     out._keep = (bm, st_, rt)
     return out
 

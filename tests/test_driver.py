@@ -181,6 +181,29 @@ def test_driver_stats_exchange_world1(ctx, tmp_path):
     assert not os.path.exists(cid)
 
 
+@pytest.mark.gpu
+def test_driver_passes_ignore_power_model(ctx, tmp_path):
+    """--power changes the job's energy scalar and nothing else: the node blocks, the user blocks, the broker's
+    delay and the user vectors appended by --node-stats / --user-stats / --vec-users come out the same with
+    and without a power model (the passes over the finished replay are handed none)."""
+    from test_node_stats import blocks
+    args = ("-f", INI, "--users", "user[6]", "--reps", "3", "--node-stats", "--user-stats", "--vec-users")
+    sa, va, sb, vb = (str(tmp_path / n) for n in ("A.sca", "A.vec", "B.sca", "B.vec"))
+    drive(*args, "--sca", sa, "--vec", va)
+    drive(*args, "--sca", sb, "--vec", vb, "--power", "100,50")
+    a, b = open(sa).read().splitlines(), open(sb).read().splitlines()
+    assert len(a) == len(b)
+    diff = [(x, y) for x, y in zip(a, b) if x != y]
+    assert len(diff) == 1 and all('"energy J"' in x and '"energy J"' in y for x, y in diff), diff
+    blk = blocks("\n".join(a))
+    assert {f"FogNet5.fogNode[{j}].udpApp[0]" for j in range(4)} <= set(blk)
+    assert {f"FogNet5.user[{u}].udpApp[0]" for u in range(6)} <= set(blk)
+    assert int(blk["FogNet5.broker.udpApp[0]"]["delay:stats"]["count"]) > 0
+    vec = open(va).read()
+    assert vec == open(vb).read()
+    assert all(vec.count(f"{sig}:vector") == 6 for sig in ("latency", "latencyH1", "taskTime")) and "delay:vector" in vec
+
+
 def test_ring_must_be_power_of_two():
     p = drive("-f", INI, "--users", "user[2]", "--ring", "1000", "--dry-run", check=False)
     assert p.returncode == 2 and "--ring must be a power of two" in p.stderr
