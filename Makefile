@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CXXFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
 SRC_DIR := fognetsimpp_amd/csrc
-SRCS := $(SRC_DIR)/capi.hip $(SRC_DIR)/replay.hip $(SRC_DIR)/replay_wide.hip $(SRC_DIR)/replay_v2.hip $(SRC_DIR)/replay_region.hip $(SRC_DIR)/decide.hip $(SRC_DIR)/tracegen.hip $(SRC_DIR)/user_stats.hip $(SRC_DIR)/node_stats.hip $(SRC_DIR)/per_user_stats.hip $(SRC_DIR)/signal_vectors.hip $(SRC_DIR)/replay_assigned.hip
+SRCS := $(SRC_DIR)/capi.hip $(SRC_DIR)/replay.hip $(SRC_DIR)/replay_wide.hip $(SRC_DIR)/replay_v2.hip $(SRC_DIR)/replay_region.hip $(SRC_DIR)/decide.hip $(SRC_DIR)/tracegen.hip $(SRC_DIR)/user_stats.hip $(SRC_DIR)/node_stats.hip $(SRC_DIR)/per_user_stats.hip $(SRC_DIR)/signal_vectors.hip $(SRC_DIR)/replay_assigned.hip $(SRC_DIR)/window_stats.hip
 HDRS := include/fognet_hip.h include/fognet_io.h $(SRC_DIR)/internal.h $(SRC_DIR)/workspace.h $(SRC_DIR)/replay_common.h $(SRC_DIR)/signals.h
 OBJDIR := build/obj
 OBJS := $(patsubst $(SRC_DIR)/%.hip,$(OBJDIR)/%.o,$(SRCS)) $(OBJDIR)/io.o
@@ -81,6 +81,9 @@ asan:
 	  -o $(ASAN_DIR)/io_users_check
 	$(HOSTCXX) $(ASAN_FLAGS) -std=c++17 -ffp-contract=off -Iinclude tests/c/io_vec_users_check.cpp $(SRC_DIR)/io.cpp \
 	  -o $(ASAN_DIR)/io_vec_users_check
+	$(HOSTCXX) $(ASAN_FLAGS) -std=c++17 -ffp-contract=off -Iinclude tests/c/io_windows_check.cpp $(SRC_DIR)/io.cpp \
+	  -o $(ASAN_DIR)/io_windows_check -Lfognetsimpp_amd -lfognet_hip -L/opt/rocm/lib -lamdhip64 \
+	  -Wl,-rpath,$(CURDIR)/fognetsimpp_amd -Wl,-rpath,/opt/rocm/lib
 	$(HOSTCXX) $(ASAN_FLAGS) -std=c++17 -ffp-contract=off -Iinclude -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ \
 	  $(SRC_DIR)/fognet_replay.cpp $(SRC_DIR)/io.cpp -o $(ASAN_DIR)/fognet_replay \
 	  -Lfognetsimpp_amd -lfognet_hip -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$(CURDIR)/fognetsimpp_amd -Wl,-rpath,/opt/rocm/lib
@@ -89,6 +92,7 @@ asan:
 	ASAN_OPTIONS=detect_leaks=1 $(ASAN_DIR)/io_nodes_check $(ASAN_DIR)
 	ASAN_OPTIONS=detect_leaks=1 $(ASAN_DIR)/io_users_check $(ASAN_DIR)
 	ASAN_OPTIONS=detect_leaks=1 $(ASAN_DIR)/io_vec_users_check $(ASAN_DIR)
+	ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/io_windows_check $(ASAN_DIR)
 	ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/fognet_replay -f tests/scenarios/fog5.ini --users 'user[10]' --reps 3 \
 	  --dry-run --show --trace-out $(ASAN_DIR)/drv.fogntrc > /dev/null
 	ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/fognet_replay -f tests/scenarios/fog5.ini -c Example --nodes 5 --dry-run > /dev/null

@@ -11,6 +11,7 @@ from .engine import (NEVER, BatchResult, V2Result, BrokerBaseApp2, BrokerBaseApp
                      generate_trace, job_from_reps, merge_job_stats, mobility_regions, power_model, reduce_stats, run_batch, run_generated, run_v2, saturating_trace, summarize,
                      summarize_moments, user_stats, sweep_params, node_stats, reduce_node_stats, merge_node_stats, summarize_node,
                      per_user_stats, reduce_user_stats, merge_user_stats, signal_vectors,
+                     window_stats, reduce_window_stats, merge_window_stats, summarize_window,
                      run_assigned, assign_round_robin, assign_random)
 from . import formats  # noqa: E402,F401
 
@@ -18,4 +19,5 @@ __all__ = ["Context", "BrokerBaseApp2", "BrokerBaseApp3", "BatchResult", "V2Resu
            "run_v2", "summarize", "summarize_moments", "user_stats", "generate_trace", "c5_params", "mobility_regions", "saturating_trace", "job_from_reps", "formats", "sweep_params", "allocate_outputs", "as_device_trace", "FognetError", "NEVER",
            "node_stats", "reduce_node_stats", "merge_node_stats", "summarize_node",
            "per_user_stats", "reduce_user_stats", "merge_user_stats", "signal_vectors",
+           "window_stats", "reduce_window_stats", "merge_window_stats", "summarize_window",
            "run_assigned", "assign_round_robin", "assign_random"]

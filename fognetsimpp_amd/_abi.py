@@ -123,6 +123,22 @@ NODE_STATS_DTYPE = np.dtype([(n, np.int64) for n in ("n_tasks", "n_queued", "n_s
 assert NODE_STATS_DTYPE.itemsize == C.sizeof(NodeStats)
 
 
+WINDOW_HEAD = (("n_publish", C.c_int64), ("n_complete", C.c_int64), ("busy_lo", C.c_uint64), ("busy_hi", C.c_uint64),
+               ("insys_lo", C.c_uint64), ("insys_hi", C.c_uint64))
+WINDOW_SIGNALS = ("queue", "delay", "latency", "latencyH1", "taskTime")
+WINDOW_MAX = 1 << 20
+WINDOW_LDS_WINDOWS = 150  # FOGNET_WINDOW_LDS_WINDOWS
+
+
+class WindowStats(C.Structure):
+    _fields_ = list(WINDOW_HEAD) + [(n, Moments) for n in WINDOW_SIGNALS]
+
+
+WINDOW_STATS_DTYPE = np.dtype([(n, np.int64 if t is C.c_int64 else np.uint64) for n, t in WINDOW_HEAD] +
+                              [(n, MOMENTS_DTYPE) for n in WINDOW_SIGNALS])
+assert WINDOW_STATS_DTYPE.itemsize == C.sizeof(WindowStats) == 408
+
+
 class BatchIn(C.Structure):
     _fields_ = [
         ("R", C.c_int32), ("T", C.c_int32), ("N", C.c_int32), ("policy", C.c_int32),
@@ -222,6 +238,11 @@ SIGNATURES = {
     "fognet_reduce_user_stats_dev": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, P]),
     "fognet_signal_vectors_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P, C.c_int32, C.c_int32,
                                             P, P, C.c_int32, C.c_int32, C.POINTER(SignalVectors), P, P]),
+    "fognet_window_stats_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P, C.c_int32, C.c_int32, P, P,
+                                          C.c_int64, C.c_int64, C.c_int32, P, P, P, P]),
+    "fognet_reduce_window_stats_dev": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, P]),
+    "fognet_window_stats_init": (None, [C.POINTER(WindowStats)]),
+    "fognet_window_stats_merge": (None, [C.POINTER(WindowStats), C.POINTER(WindowStats)]),
     "fognet_user_stats_init": (None, [C.POINTER(UserStats)]),
     "fognet_user_stats_merge": (None, [C.POINTER(UserStats), C.POINTER(UserStats)]),
     "fognet_job_stats_init": (None, [C.POINTER(JobStats)]),
@@ -248,6 +269,8 @@ SIGNATURES = {
     "fognet_write_vec": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P, P, P, P, P, P]),
     "fognet_write_vec_users": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P, P, P, P,
                                          C.c_int]),
+    "fognet_write_vec_windows": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int64,
+                                           C.c_int64, C.c_int64, P, C.c_int32, C.c_int]),
     "fognet_gen_trace_mqtt": (C.c_int, [C.c_uint32, C.c_int32, P, P, P, P, C.c_int64, C.c_int32, C.c_int32,
                                         C.c_int32, P, P, P, C.POINTER(C.c_int32)]),
 }

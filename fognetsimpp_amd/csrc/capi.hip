@@ -836,7 +836,7 @@ int fognet_run_batch(fognet_ctx* c, const fognet_batch_in* in, fognet_batch_out*
 }
 
 // ---------------------------------------------------------------- passes over a finished replay
-// What the four passes share of their entry points; each keeps its own checks, in its own order, between them.
+// What the five passes share of their entry points; each keeps its own checks, in its own order, between them.
 struct PassSpec {
   bool need_start;    // the pass reads start_tick as well as node, status and done_tick
   bool hier_refused;  // EXT_HIER: refused outright; else only without fognet_batch_out.escalated
@@ -938,7 +938,63 @@ int fognet_per_user_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fo
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "per-user stats launch");
 }
 
+int fognet_window_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out,
+                            const int32_t* user_of, int32_t U, int32_t link_stride, const int64_t* user_ul,
+                            const int64_t* user_dl, int64_t t0, int64_t window, int32_t W, fognet_window_stats* win,
+                            int64_t* n_outside, int64_t* n_unassigned, void* stream) {
+  static const PassSpec spec = {true, false, "window statistics under EXT_HIER: an escalated task reaches its node, "
+                                             "and sends its acks, hier_up_tick later, and " FOGNET_NEEDS_ESCALATED};
+  static_assert(FOGNET_WINDOW_MAX == 1 << 20, "the message below");
+  fognet::ReplayArgs a;
+  int rc = pass_begin(c, in, out, spec, &a);
+  if (rc) return rc;
+  if (U < 0) return fail(c, FOGNET_ERR_ARG, "negative U");
+  if (link_stride != 0 && link_stride != U) return fail(c, FOGNET_ERR_ARG, "link_stride must be 0 or U");
+  if (window < 1 || t0 < 0 || W < 0) return fail(c, FOGNET_ERR_ARG, "window_tick >= 1, t0_tick >= 0 and W >= 0");
+  if (W > FOGNET_WINDOW_MAX) return fail(c, FOGNET_ERR_UNSUPPORTED, "window statistics: W > 1048576 windows");
+  const int64_t kEnd = (int64_t)1 << 62;  // (W <= 2^20: the quotient cannot wrap)
+  if (W > 0 && (window > kEnd / W || t0 > kEnd - (int64_t)W * window))
+    return fail(c, FOGNET_ERR_ARG, "t0_tick + W * window_tick must not pass 2^62");
+  if (t0 > kEnd) return fail(c, FOGNET_ERR_ARG, "t0_tick + W * window_tick must not pass 2^62");
+  if (a.R == 0) return FOGNET_OK;
+  if (!out->stats) return fail(c, FOGNET_ERR_ARG, "null stats");
+  if (!has_task_outputs(a, out, spec))
+    return fail(c, FOGNET_ERR_ARG, "window statistics need the per-task outputs, start_tick included");
+  if (W > 0 && !win) return fail(c, FOGNET_ERR_ARG, "null win");
+  if (a.T > 0 && U > 0 && !user_of) return fail(c, FOGNET_ERR_ARG, "null user_of");
+  if (U > 0 && (!user_ul || !user_dl)) return fail(c, FOGNET_ERR_ARG, "null user links");
+  if ((rc = pass_bind(c, out, spec, &a))) return rc;
+  // FOGNET_WINDOW_STATS=hbm: the accumulators are the caller's records and the workspace for every W
+  // (the layout of W > FOGNET_WINDOW_LDS_WINDOWS), so small tests run both layouts on the same traces
+  const bool force_hbm = env_is("FOGNET_WINDOW_STATS", "hbm");
+  const size_t delta_n = fognet::window_stats_delta_count(a.R, W, force_hbm);
+  fognet::WindowWs w{};
+  if (delta_n > 0) {
+    fognet::WsCursor measure{nullptr};
+    rc = ensure(c, (void**)&c->ring, &c->ring_bytes, fognet::window_stats_ws(w, delta_n, measure), "window cover counts");
+    if (rc) return rc;
+    fognet::WsCursor carve{reinterpret_cast<unsigned char*>(c->ring)};
+    (void)fognet::window_stats_ws(w, delta_n, carve);
+  }
+  const fognet::UserLinks users{user_of, user_ul, user_dl, U, link_stride};
+  const hipError_t e = fognet::launch_window_stats(a, users, t0, window, W, win, n_outside, n_unassigned, w.delta,
+                                                   force_hbm, (hipStream_t)stream);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "window stats launch");
+}
+
 #undef FOGNET_NEEDS_ESCALATED
+
+int fognet_reduce_window_stats_dev(fognet_ctx* c, const fognet_window_stats* win, const fognet_rep_stats* stats,
+                                   int32_t R, int32_t W, fognet_window_stats* out, void* stream) {
+  if (!c) return FOGNET_ERR_ARG;
+  if (R < 0 || W < 0) return fail(c, FOGNET_ERR_ARG, "negative R/W");
+  if (W == 0) return FOGNET_OK;
+  if (!out || (R > 0 && (!win || !stats))) return fail(c, FOGNET_ERR_ARG, "null pointer");
+  const int rc = set_device(c);
+  if (rc) return rc;
+  const hipError_t e = fognet::launch_reduce_window_stats(win, stats, R, W, out, (hipStream_t)stream);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "window reduce launch");
+}
 
 int fognet_signal_vectors_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out,
                               const int32_t* user_of, int32_t U, int32_t link_stride, const int64_t* user_ul,
@@ -1165,6 +1221,33 @@ void fognet_user_stats_init(fognet_user_stats* s) {
 
 void fognet_user_stats_merge(fognet_user_stats* a, const fognet_user_stats* b) {
   if (!a || !b) return;
+  moments_merge_host(&a->delay, &b->delay);
+  moments_merge_host(&a->latency, &b->latency);
+  moments_merge_host(&a->latencyH1, &b->latencyH1);
+  moments_merge_host(&a->taskTime, &b->taskTime);
+}
+
+void fognet_window_stats_init(fognet_window_stats* s) {
+  if (!s) return;
+  memset(s, 0, sizeof *s);
+  moments_init_host(&s->queue);
+  moments_init_host(&s->delay);
+  moments_init_host(&s->latency);
+  moments_init_host(&s->latencyH1);
+  moments_init_host(&s->taskTime);
+}
+
+void fognet_window_stats_merge(fognet_window_stats* a, const fognet_window_stats* b) {
+  if (!a || !b) return;
+  a->n_publish += b->n_publish;
+  a->n_complete += b->n_complete;
+  unsigned __int128 s = (unsigned __int128)a->busy_lo + b->busy_lo;
+  a->busy_lo = (uint64_t)s;
+  a->busy_hi = a->busy_hi + b->busy_hi + (uint64_t)(s >> 64);
+  s = (unsigned __int128)a->insys_lo + b->insys_lo;
+  a->insys_lo = (uint64_t)s;
+  a->insys_hi = a->insys_hi + b->insys_hi + (uint64_t)(s >> 64);
+  moments_merge_host(&a->queue, &b->queue);
   moments_merge_host(&a->delay, &b->delay);
   moments_merge_host(&a->latency, &b->latency);
   moments_merge_host(&a->latencyH1, &b->latencyH1);

@@ -342,6 +342,8 @@ struct Options {
   int policy = FOGNET_POLICY_REF_V3;
   int assign = 0;            // --assign: 0 the broker decides, 1 round-robin, 2 random
   uint64_t assign_seed = 0;  // --assign random:SEED
+  int64_t window_tick = 0;   // --windows DT[,W]: the window length (0: no window vectors)
+  int32_t windows = 0;       // ... and their number (0: ceil(stop / DT))
   double p_busy = -1.0, p_idle = -1.0;
 };
 
@@ -484,6 +486,9 @@ void usage() {
       "  --node-stats         with --sca: append one block per fog node (tasks, queueTime, response)\n"
       "  --vec-users          with --vec (BrokerBaseApp3 runs from an ini): append replication 0's delay vector and\n"
       "                       every user module's latency, latencyH1 and taskTime vectors, in emission order\n"
+      "  --windows DT[,W]     with --vec (BrokerBaseApp3 runs from an ini): append the job's statistics per window of\n"
+      "                       DT sim time from 0 (W windows; default ceil(stop / DT)): utilisation, tasks in system,\n"
+      "                       completions, publishes and the mean and count of the five signals, over all replications\n"
       "  --user-stats         with --sca (BrokerBaseApp3 runs from an ini): append one block per user module\n"
       "                       (latency, latencyH1, taskTime) and the broker's delay\n"
       "  --device D           HIP device (default 0)\n"
@@ -552,6 +557,17 @@ Options parse_args(int argc, char** argv) {
     else if (a == "--node-stats") o.node_stats = true;
     else if (a == "--user-stats") o.user_stats = true;
     else if (a == "--vec-users") o.vec_users = true;
+    else if (a == "--windows") {
+      const std::vector<std::string> p = split(need(i), ',');
+      if (p.empty() || p.size() > 2) die("--windows DT[,W]");
+      o.window_tick = parse_time(p[0], "--windows");
+      if (o.window_tick < 1) die("--windows: DT must be positive");
+      if (p.size() == 2) {
+        const long long w = parse_int(p[1], "--windows DT,W");
+        if (w < 1 || w > FOGNET_WINDOW_MAX) die("--windows: W must lie in [1, 1048576]");
+        o.windows = (int32_t)w;
+      }
+    }
     else if (a == "--world") o.world = (int)parse_int(need(i), "--world");
     else if (a == "--rank") o.rank = (int)parse_int(need(i), "--rank");
     else if (a == "--comm-id") o.comm_id = need(i);
@@ -571,6 +587,10 @@ Options parse_args(int argc, char** argv) {
   if (o.vec_users && o.vec.empty()) die("--vec-users appends to replication 0's .vec: give --vec FILE");
   if (o.vec_users && !o.trace_in.empty()) die("--vec-users needs the ini's user modules (-f INI): a trace file names no users");
   if (o.vec_users && o.user_dl < 0) die("--vec-users needs a broker->user latency (--user-dl none gives the acks no way back)");
+  if (o.window_tick && o.vec.empty()) die("--windows appends to the .vec: give --vec FILE");
+  if (o.window_tick && o.world > 1) die("--windows: the window records of several ranks are not combined (--world 1)");
+  if (o.window_tick && !o.trace_in.empty()) die("--windows needs the ini's user modules and stop time (-f INI)");
+  if (o.window_tick && o.user_dl < 0) die("--windows needs a broker->user latency (--user-dl none gives the acks no way back)");
   if (o.assign && o.policy_set) die("--assign replaces the broker's decision: not together with --policy");
   if (o.world > 1 && o.comm_id.empty()) die("--world > 1 needs --comm-id FILE (the communicator id's rendezvous)");
   if (o.reps < o.world) die("--reps must be >= --world (every rank replays a block of replications)");
@@ -834,6 +854,55 @@ void append_user_vectors(const Options& o, fognet_ctx* ctx, const DeviceBatch& d
         "vec users");
 }
 
+// --windows: the window records of every replication (fognet_window_stats_dev; links as for --user-stats),
+// reduced over the replications (fognet_reduce_window_stats_dev) and appended to the .vec as fourteen vectors
+// with a row per window.  The summary names the point events outside [0, W * DT): before it, at or past its end.
+void append_window_vectors(const Options& o, fognet_ctx* ctx, const DeviceBatch& db, const UserSide& us,
+                           const std::string& network, const std::string& run_id, int64_t stop, int32_t id_base) {
+  const fognet_batch_in din = db.pass_in();
+  const fognet_batch_out dout = db.pass_out();
+  const size_t R = (size_t)din.R;
+  const int32_t U = (int32_t)us.modules.size();
+  int64_t W64 = o.windows ? o.windows : (std::max<int64_t>(stop, 1) + o.window_tick - 1) / o.window_tick;
+  if (W64 > FOGNET_WINDOW_MAX) die("--windows: more than 1048576 windows up to the stop time (give a longer DT, or DT,W)");
+  const int32_t W = (int32_t)W64;
+  DeviceMem mem;
+  int32_t* d_user_of = mem.copy(us.user_of);
+  int64_t* d_ul = mem.copy(std::vector<int64_t>(U, o.user_ul));
+  int64_t* d_dl = mem.copy(std::vector<int64_t>(U, o.user_dl));
+  fognet_window_stats* d_win = mem.alloc<fognet_window_stats>(R * (size_t)W);
+  fognet_window_stats* d_job = mem.alloc<fognet_window_stats>((size_t)W);
+  int64_t* d_outside = mem.alloc<int64_t>(2 * R);
+  int64_t* d_un = mem.alloc<int64_t>(R);
+  mem.must();
+  check_ctx(ctx, fognet_window_stats_dev(ctx, &din, &dout, d_user_of, U, 0, d_ul, d_dl, 0, o.window_tick, W, d_win, d_outside,
+                                         d_un, nullptr),
+            "fognet_window_stats_dev");
+  check_ctx(ctx, fognet_reduce_window_stats_dev(ctx, d_win, dout.stats, din.R, W, d_job, nullptr),
+            "fognet_reduce_window_stats_dev");
+  std::vector<fognet_window_stats> job((size_t)W);
+  std::vector<int64_t> outside(2 * R), un(R);
+  std::vector<fognet_rep_stats> stats(R);
+  mem.fetch(job.data(), d_job, (size_t)W), mem.fetch(outside.data(), d_outside, 2 * R), mem.fetch(un.data(), d_un, R);
+  mem.fetch(stats.data(), dout.stats, R);
+  mem.must();
+  int64_t total[2] = {0, 0};
+  int64_t merged = 0;  // the replications the job reduction took
+  for (size_t r = 0; r < R; ++r) {
+    if (un[r] != 0)
+      die("--windows: replication " + std::to_string(r) + " has " + std::to_string(un[r]) + " publishes of no known user");
+    if (stats[r].status != FOGNET_OK) continue;
+    ++merged;
+    total[0] += outside[2 * r], total[1] += outside[2 * r + 1];
+  }
+  check(fognet_write_vec_windows(o.vec.c_str(), run_id.c_str(), network.c_str(), din.N, W, 0, o.window_tick,
+                                 std::max<int64_t>(merged, 1), job.data(), id_base, 1),
+        "vec windows");
+  if (!o.quiet)
+    std::printf("windows=%d window_ticks=%" PRId64 " replications=%" PRId64 " events_before=%" PRId64 " events_after=%" PRId64
+                "\n", W, o.window_tick, merged, total[0], total[1]);
+}
+
 // --assign: the rule's name for the run attributes and the summary
 std::string assign_name(const Options& o) {
   return o.assign == 1 ? "rr" : "random:" + std::to_string(o.assign_seed);
@@ -873,7 +942,7 @@ void add_run_attr(const std::string& path, const std::string& name, const std::s
 
 // BrokerBaseApp3 + ComputeBrokerApp3 (the batch engine; device entry points over one device copy of the batch).
 int run_v3(const Options& o, fognet_batch_in in, const std::string& network, const std::string& run_id,
-           const UserSide* us = nullptr, int r0 = 0) {
+           const UserSide* us = nullptr, int r0 = 0, int64_t stop = 0) {
   const size_t RT = (size_t)in.R * (size_t)in.T;
   std::vector<int32_t> node(RT);
   std::vector<uint8_t> status(RT);
@@ -929,6 +998,9 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
           "vec");
     if (o.assign) add_run_attr(o.vec, "assign", assign_name(o));
     if (o.vec_users && us) append_user_vectors(o, ctx, *db, *us, network, run_id);
+    if (o.window_tick && us)  // after the ids of fognet_write_vec and, where they were written, fognet_write_vec_users
+      append_window_vectors(o, ctx, *db, *us, network, run_id, stop,
+                            in.N + 1 + (o.vec_users ? 1 + 3 * (int32_t)us->modules.size() : 0));
   }
   if (!o.quiet) {
     std::printf("policy=%s R=%d T=%d N=%d decisions=%" PRId64 " queued=%" PRId64 " started=%" PRId64
@@ -1075,6 +1147,8 @@ int main(int argc, char** argv) {
     die("--user-stats applies to BrokerBaseApp3 runs (the BrokerBaseApp2 model has no closed form for the user signals)");
   if (v2 && o.vec_users)
     die("--vec-users applies to BrokerBaseApp3 runs (the BrokerBaseApp2 model has no closed form for the user signals)");
+  if (v2 && o.window_tick)
+    die("--windows applies to BrokerBaseApp3 runs (the BrokerBaseApp2 replay keeps no closed form for the signals)");
   const int32_t N = (int32_t)sc.mips.size();
   // BrokerBaseApp2 does not answer a user's CONNECT with a CONNACK, so its
   // users publish from startTime + sendInterval on
@@ -1086,7 +1160,7 @@ int main(int argc, char** argv) {
   const int r0 = o.rank * q + std::min(o.rank, rem), nr = q + (o.rank < rem ? 1 : 0);
   UserSide us;
   us.modules = sc.users;
-  const int32_t T = gen_traces(sc, o, user_dl, r0, nr, arrive, req, o.user_stats || o.vec_users ? &us.user_of : nullptr);
+  const int32_t T = gen_traces(sc, o, user_dl, r0, nr, arrive, req, o.user_stats || o.vec_users || o.window_tick ? &us.user_of : nullptr);
 
   // node k: CONNECT at startTime reaches the broker after ul, the CONNACK
   // comes back after dl, the first ADVERTISEMIPS fires 0.01 s later
@@ -1152,5 +1226,5 @@ int main(int argc, char** argv) {
     if (o.world > 1) die("BrokerBaseApp2 replays run on one GPU (--world 1)");
     return run_v2(o, sc, T, arrive, req, dl, ul, first_adv, run_id);
   }
-  return run_v3(o, in, sc.network, run_id, o.user_stats || o.vec_users ? &us : nullptr, r0);
+  return run_v3(o, in, sc.network, run_id, o.user_stats || o.vec_users || o.window_tick ? &us : nullptr, r0, sc.stop);
 }

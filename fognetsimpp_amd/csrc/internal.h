@@ -453,6 +453,16 @@ int32_t signal_vectors_sort_lds_max();
 hipError_t launch_signal_vectors(const ReplayArgs& a, const UserLinks& users, int32_t r0, int32_t Rv,
                                  const fognet_signal_vectors& vec, int64_t* n_unassigned, uint32_t* cursor,
                                  bool force_hbm, int stages, hipStream_t s);
+// Statistics per window of sim time and their job reduction (window_stats.hip).  Up to
+// FOGNET_WINDOW_LDS_WINDOWS windows the records and the cover-count deltas live in LDS unless
+// force_hbm; else the deltas are ws_delta, window_stats_delta_count() words of the workspace
+// (WindowWs), which the kernel zeroes itself.  The reduction is one workgroup per window.
+size_t window_stats_delta_count(int32_t R, int32_t W, bool force_hbm);
+hipError_t launch_window_stats(const ReplayArgs& a, const UserLinks& users, int64_t t0, int64_t window, int32_t W,
+                               fognet_window_stats* out, int64_t* n_outside, int64_t* n_unassigned, int64_t* ws_delta,
+                               bool force_hbm, hipStream_t s);
+hipError_t launch_reduce_window_stats(const fognet_window_stats* in, const fognet_rep_stats* stats, int32_t R, int32_t W,
+                                      fognet_window_stats* out, hipStream_t s);
 // Assigned replay (replay_assigned.hip): the node model under the caller's decisions assign [R][T],
 // a validation + count kernel and one wavefront per replication over tiles of 64 tasks.  Fills
 // a.out_node/out_status/out_start/out_done and the replay fields of a.out_stats; stats: the whole

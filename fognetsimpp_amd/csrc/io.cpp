@@ -626,6 +626,75 @@ int fognet_write_vec_users(const char* path, const char* run_id, const char* net
   return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_vec_users: write failed: ") + path);
 }
 
+int fognet_write_vec_windows(const char* path, const char* run_id, const char* network, int32_t N, int32_t W,
+                             int64_t t0_tick, int64_t window_tick, int64_t replications, const fognet_window_stats* job,
+                             int32_t id_base, int append) {
+  if (!path || !run_id || !network || N <= 0 || W < 0 || t0_tick < 0 || window_tick < 1 || replications < 1 ||
+      id_base < 0 || (W > 0 && !job))
+    return fail(FOGNET_ERR_ARG, "write_vec_windows: bad argument");
+  if (W > 0 && (window_tick > ((int64_t)1 << 62) / W || t0_tick > ((int64_t)1 << 62) - W * window_tick))
+    return fail(FOGNET_ERR_ARG, "write_vec_windows: t0_tick + W * window_tick must not pass 2^62");
+  FILE* f = fopen(path, append ? "a" : "w");
+  if (!f) return fail(FOGNET_ERR_ARG, std::string("write_vec_windows: cannot open ") + path);
+  if (!append) run_header(f, run_id, network);
+  const std::string net = network;
+  const std::string nodes = net + ".fogNodes.udpApp[0]", broker = net + ".broker.udpApp[0]", users = net + ".users.udpApp[0]";
+  long long id = id_base;
+  auto declare = [&](const std::string& mod, const char* source, const char* name) {
+    fprintf(f, "vector %lld  %s  %s  TV\n", id++, mod.c_str(), name);
+    fprintf(f, "attr interpolationmode  none\nattr source  %s\nattr title  \"%s\"\n", source, name);
+  };
+  // vector ids from id_base, in this order
+  declare(nodes, "busy", "utilisation:window");
+  declare(nodes, "tasksInSystem", "tasksInSystem:window");
+  declare(nodes, "completions", "completions:window");
+  declare(nodes, "queueTime", "queueTime:window(mean)");
+  declare(nodes, "queueTime", "queueTime:window(count)");
+  declare(broker, "publishes", "publishes:window");
+  declare(broker, "delay", "delay:window(mean)");
+  declare(broker, "delay", "delay:window(count)");
+  const char* names[3] = {"latency", "latencyH1", "taskTime"};
+  for (int s = 0; s < 3; ++s) {
+    declare(users, names[s], (std::string(names[s]) + ":window(mean)").c_str());
+    declare(users, names[s], (std::string(names[s]) + ":window(count)").c_str());
+  }
+  // one row per window at the window's end; a mean has no row where nothing was emitted
+  auto end_of = [&](int32_t w) { return simtime_str(t0_tick + ((int64_t)w + 1) * window_tick); };
+  auto rows = [&](long long v, auto&& value) {
+    for (int32_t w = 0; w < W; ++w) {
+      const std::string s = value(job[w]);
+      if (!s.empty()) fprintf(f, "%lld\t%s\t%s\n", v, end_of(w).c_str(), s.c_str());
+    }
+  };
+  auto ticks128 = [](uint64_t lo, uint64_t hi) { return (long double)hi * 18446744073709551616.0L + (long double)lo; };
+  auto count = [](int64_t n) { return std::to_string((long long)n); };
+  // the mean of the raw values from their exact sum (recorded value raw * 1e-12: ms, delay s)
+  auto mean = [](const fognet_moments& m) {
+    if (m.count <= 0) return std::string();
+    const uint64_t S[3] = {m.sum_lo, m.sum_hi, (int64_t)m.sum_hi < 0 ? ~(uint64_t)0 : 0};
+    const uint64_t Q[3] = {m.sq_lo, m.sq_hi, m.sq_top};
+    return num(moments(m.count, S, Q, m.min_raw, m.max_raw, true, true).mean);
+  };
+  const long double span = (long double)window_tick * (long double)replications;
+  rows(id_base + 0, [&](const fognet_window_stats& r) { return num((double)(ticks128(r.busy_lo, r.busy_hi) / (span * N))); });
+  rows(id_base + 1, [&](const fognet_window_stats& r) { return num((double)(ticks128(r.insys_lo, r.insys_hi) / span)); });
+  rows(id_base + 2, [&](const fognet_window_stats& r) { return count(r.n_complete); });
+  rows(id_base + 3, [&](const fognet_window_stats& r) { return mean(r.queue); });
+  rows(id_base + 4, [&](const fognet_window_stats& r) { return count(r.queue.count); });
+  rows(id_base + 5, [&](const fognet_window_stats& r) { return count(r.n_publish); });
+  rows(id_base + 6, [&](const fognet_window_stats& r) { return mean(r.delay); });
+  rows(id_base + 7, [&](const fognet_window_stats& r) { return count(r.delay.count); });
+  const fognet_moments fognet_window_stats::*sig[3] = {&fognet_window_stats::latency, &fognet_window_stats::latencyH1,
+                                                       &fognet_window_stats::taskTime};
+  for (int s = 0; s < 3; ++s) {
+    rows(id_base + 8 + 2 * s, [&](const fognet_window_stats& r) { return mean(r.*sig[s]); });
+    rows(id_base + 9 + 2 * s, [&](const fognet_window_stats& r) { return count((r.*sig[s]).count); });
+  }
+  const bool ok = ferror(f) == 0;
+  return (fclose(f) == 0 && ok) ? FOGNET_OK
+                                : fail(FOGNET_ERR_ARG, std::string("write_vec_windows: write failed: ") + path);
+}
+
 int fognet_gen_trace_mqtt(uint32_t seed, int32_t U, const int64_t* start_tick, const int64_t* interval_tick,
                           const int64_t* uplink_tick, const int64_t* downlink_tick, int64_t stop_tick,
                           int32_t req_base, int32_t req_span, int32_t cap, int64_t* arrive_tick, int32_t* req_mips,

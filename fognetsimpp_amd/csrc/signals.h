@@ -1,5 +1,5 @@
 // signals.h — what the passes over a finished replay share (user_stats.hip, node_stats.hip,
-// per_user_stats.hip, signal_vectors.hip), each stated once: which replications and tasks a
+// per_user_stats.hip, signal_vectors.hip, window_stats.hip), each stated once: which replications and tasks a
 // pass reads, the per-task row and the loop that streams it, the emission rule of a decided
 // publish, the moments of one signal with their wave merge and atomic commit, the empty
 // record, the frame of a pass keyed by node or user, and the job reduction of its records.

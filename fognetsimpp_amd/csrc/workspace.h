@@ -95,6 +95,19 @@ inline size_t signal_vectors_ws(VecWs& w, size_t Rv, size_t V, WsCursor& v) {
   return v.off;
 }
 
+// Window statistics (window_stats.hip): [deltas].  Two cover-count deltas (busy, insys) per
+// (replication, window): the difference arrays of the windows that an interval covers whole,
+// zeroed by the kernel itself.  delta_n = R * W * 2 above the kernel's LDS capacity or when the
+// workspace layout is forced, else 0 (the deltas then live in LDS beside the records).
+struct WindowWs {
+  int64_t* delta;  // [R][W][2]
+};
+
+inline size_t window_stats_ws(WindowWs& w, size_t delta_n, WsCursor& v) {
+  v(w.delta, delta_n);
+  return v.off;
+}
+
 // Assigned replay (replay_assigned.hip): [refusal flags | node offsets | advert rows || carries].
 // off: the exclusive scan of the tasks per node, one row of N + 1 per replication; adv: every
 // task's completion advert tick, grouped by node in trace order (row off[k] + rank); the five

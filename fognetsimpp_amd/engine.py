@@ -716,6 +716,75 @@ def merge_user_stats(records) -> np.ndarray:
     return np.frombuffer(bytes(acc), dtype=_abi.USER_STATS_DTYPE).copy()
 
 
+def window_stats(ctx: Context, trace: dict, out: BatchResult, user_of, user_ul, user_dl, t0: int, window: int, W: int,
+                 policy: str | int | None = None, res: torch.Tensor | None = None, hier_up_tick: int | None = None,
+                 n_outside: torch.Tensor | None = None, n_unassigned: torch.Tensor | None = None):
+    """Statistics per window of sim time (fognet_window_stats_dev) of a finished replay on the
+    current stream: window w covers the ticks [t0 + w * window, t0 + (w + 1) * window), w < W.
+    ``user_of`` / ``user_ul`` / ``user_dl``: as :func:`per_user_stats`; all three None: no user
+    side (U = 0).  Returns ``(records, n_outside, n_unassigned)``: the device buffer uint8
+    [R, W * sizeof(fognet_window_stats)] (``.cpu().numpy().view(_abi.WINDOW_STATS_DTYPE)`` gives
+    [R, W] records), the int64 [R, 2] device tensor of point events before and at or past the
+    range, and the int64 [R] device tensor of decided publishes whose user lies outside [0, U)
+    (they keep their node-side events; nothing is raised for them).  ``res`` / ``n_outside`` /
+    ``n_unassigned``: write into these buffers instead of new ones.  ``policy`` and
+    ``hier_up_tick``: as for :func:`user_stats`; EXT_HIER needs ``out.escalated`` and is refused
+    without it."""
+    dims = R, T, _, _ = _dims(trace)
+    dev = trace["arrive"].device
+    if user_of is None and user_ul is None and user_dl is None:
+        uo = uu = ud = None
+        U = link_stride = 0
+    else:
+        uo, uu, ud, U, link_stride = _user_tables(user_of, user_ul, user_dl, R, T, dev)
+    nres = R * max(W, 0) * _abi.WINDOW_STATS_DTYPE.itemsize
+    res = _record_buffer(res, nres, dev, "res", alloc=max(nres, 1))
+    cnt = []
+    for t, shape, what in ((n_outside, (R, 2), "n_outside"), (n_unassigned, (R,), "n_unassigned")):
+        t = t if t is not None else torch.empty(shape, dtype=torch.int64, device=dev)
+        if t.dtype != torch.int64 or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            raise FognetError(_abi.FOGNET_ERR_ARG, f"{what} must be a contiguous int64 {list(shape)} tensor on the "
+                                                   f"trace's device")
+        cnt.append(t)
+    bi, bo = _pass_descriptors(trace, out, dims, _policy_of(out, policy), hier_up_tick)
+    ctx.check(ctx._lib.fognet_window_stats_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(uo), U, link_stride,
+                                               _ptr(uu), _ptr(ud), t0, window, W, _ptr(res), _ptr(cnt[0]),
+                                               _ptr(cnt[1]), _stream_ptr(dev)), "window_stats")
+    return res[:nres].view(R, max(W, 0) * _abi.WINDOW_STATS_DTYPE.itemsize), cnt[0], cnt[1]
+
+
+def reduce_window_stats(ctx: Context, win: torch.Tensor, stats: torch.Tensor, R: int, W: int,
+                        out: torch.Tensor | None = None) -> np.ndarray:
+    """Exact job reduction of window records on the device (fognet_reduce_window_stats_dev):
+    record w merges window w over the replications whose status is OK.  ``win``:
+    :func:`window_stats`'s buffer; ``stats``: the replications' records (BatchResult.stats).
+    Returns WINDOW_STATS_DTYPE [W]; ``out``: the device buffer written to (uint8,
+    W * sizeof(fognet_window_stats))."""
+    nout = W * _abi.WINDOW_STATS_DTYPE.itemsize
+    dev = stats.device
+    out = _record_buffer(out, nout, dev, "out", alloc=max(nout, 1))
+    if win.numel() < R * nout or stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "win / stats smaller than R replications")
+    ctx.check(ctx._lib.fognet_reduce_window_stats_dev(ctx.handle, _ptr(win), _ptr(stats), R, W, _ptr(out),
+                                                      _stream_ptr(dev)), "reduce_window_stats")
+    return out[:nout].cpu().numpy().view(_abi.WINDOW_STATS_DTYPE)
+
+
+def merge_window_stats(records) -> np.ndarray:
+    """Exact host merge of window record arrays [W] (e.g. one per GPU after an all-gather;
+    fognet_window_stats_merge) into one [W]."""
+    lib = _abi.load()
+    records = [np.ascontiguousarray(r, dtype=_abi.WINDOW_STATS_DTYPE).reshape(-1) for r in records]
+    W = records[0].size if records else 0
+    acc = (_abi.WindowStats * W)()
+    for w in range(W):
+        lib.fognet_window_stats_init(C.byref(acc[w]))
+        for rec in records:
+            b = _abi.WindowStats.from_buffer_copy(rec[w].tobytes())
+            lib.fognet_window_stats_merge(C.byref(acc[w]), C.byref(b))
+    return np.frombuffer(bytes(acc), dtype=_abi.WINDOW_STATS_DTYPE).copy()
+
+
 @dataclass
 class V2Result:
     node: torch.Tensor        # [R, T] int32 (-1: served by the broker / no node)
@@ -806,6 +875,21 @@ def summarize_node(rec) -> dict:
             "lost": int(rec["n_lost"]), "busy_s": int(rec["busy_s"]),
             "last_tick": int(rec["last_tick"]) if int(rec["resp"]["count"]) else None,
             "queueTime_ms": summarize_moments(rec["queue"]), "response_ms": resp}
+
+
+def summarize_window(rec, N: int, window: int, reps: int = 1) -> dict:
+    """`.sca`-style view of one window record (WINDOW_STATS_DTYPE) of ``reps`` merged replications
+    with ``N`` nodes and windows of ``window`` ticks: the counts, the two time averages
+    (utilisation = busy / (N * window * reps), tasks in system = insys / (window * reps)) and the
+    five signals' fields (delay in ms from ticks, the others raw values * 1e-12 ms)."""
+    busy = int(rec["busy_lo"]) | (int(rec["busy_hi"]) << 64)
+    insys = int(rec["insys_lo"]) | (int(rec["insys_hi"]) << 64)
+    span = window * max(reps, 1)
+    return {"publishes": int(rec["n_publish"]), "completions": int(rec["n_complete"]),
+            "utilisation": busy / (N * span), "tasks_in_system": insys / span,
+            "queueTime_ms": summarize_moments(rec["queue"]), "delay_ms": summarize_moments(rec["delay"], raw_ms=False),
+            "latency_ms": summarize_moments(rec["latency"]), "latencyH1_ms": summarize_moments(rec["latencyH1"]),
+            "taskTime_ms": summarize_moments(rec["taskTime"])}
 
 
 def reduce_stats(ctx: Context, stats: torch.Tensor, R: int, out: torch.Tensor | None = None) -> np.ndarray:

@@ -167,6 +167,18 @@ def write_vec_users(path: str, offset, time, value, U: int, id_base: int = 0, us
                                               1 if append else 0), "write_vec_users")
 
 
+def write_vec_windows(path: str, job, N: int, t0: int, window: int, replications: int, id_base: int = 0,
+                      append: bool = False, run_id: str = "General-0-fognet", network: str = "FogNet") -> None:
+    """A job's window records (WINDOW_STATS_DTYPE [W], the merge of ``replications`` replications of
+    ``N`` nodes) as fourteen OMNeT++ `.vec` vectors with a row per window at its end time
+    (fognet_write_vec_windows): utilisation, tasks in system, completions, publishes, and the mean
+    and count of the five signals.  ``append``: add the vectors to a file :func:`write_vec` /
+    :func:`write_vec_users` wrote (``id_base``: the first free vector id)."""
+    rec = np.ascontiguousarray(job, dtype=_abi.WINDOW_STATS_DTYPE).reshape(-1)
+    _check(_abi.load().fognet_write_vec_windows(path.encode(), run_id.encode(), network.encode(), N, rec.size, t0, window,
+                                                replications, _p(rec), id_base, 1 if append else 0), "write_vec_windows")
+
+
 def gen_trace_mqtt(seed: int, start, interval, uplink, downlink, stop: int, req_base: int = 200, req_span: int = 701,
                    cap: int | None = None) -> dict:
     """Reference task source (fognet_gen_trace_mqtt): per-user tick arrays

@@ -349,6 +349,10 @@ typedef struct fognet_batch_out {
  *     [Rv][cap], n_unassigned [Rv]) likewise: 8-B alignment (task: 4 B), nothing outside them
  *     touched, no initialisation needed; rows at and past offset[V] keep what they held; a
  *     failed replication's offsets are all 0 and none of its rows is written.
+ *   The window records (fognet_window_stats_dev's [R][W], fognet_reduce_window_stats_dev's [W]),
+ *     n_outside [R][2] and n_unassigned [R] likewise: 8-B alignment, nothing outside them
+ *     touched, no initialisation needed; a failed replication's row is W empty records and
+ *     its n_outside and n_unassigned are 0.
  *   escalated likewise: 1-B alignment, nothing outside [R][T] touched, no initialisation
  *     needed; a failed replication's row is undefined, like its other per-task rows.
  *   The assignment (fognet_replay_assigned_dev's and fognet_run_assigned_dev's assign [R][T])
@@ -752,6 +756,83 @@ int fognet_signal_vectors_dev(fognet_ctx *ctx, const fognet_batch_in *in, const 
                               const int32_t *user_of, int32_t U, int32_t link_stride,
                               const int64_t *user_ul_tick, const int64_t *user_dl_tick, int32_t r0, int32_t Rv,
                               const fognet_signal_vectors *vec, int64_t *n_unassigned, void *hip_stream);
+
+/* Time-window statistics.  Window w of a call covers the ticks [t0_tick + w * window_tick,
+ * t0_tick + (w + 1) * window_tick), w in [0, W); the covered range is their union.  One record
+ * holds what happened in one window of one replication (or, reduced, of one job).
+ * Point events fall into the window of their own tick.  The emissions of the five signals, their
+ * times and their values are the rows of "Signal vectors" above, with the same emission rule and
+ * the same links; only two things are added here: n_publish falls at arrive_tick and n_complete
+ * at done_tick, and under FOGNET_POLICY_EXT_HIER the node's first ack of an escalated task leaves
+ * hier_up_tick later, as in fognet_per_user_stats_dev.  An emission whose value leaves the
+ * simtime_t range is no row there; here it counts in `overflow` of the window of its time, as in
+ * the other records.
+ * Intervals are clipped to the covered range, and each window receives the ticks of the interval
+ * that lie in it; an interval of length zero adds nothing.  Over a range that covers a
+ * replication whole, the busy sums add up to 10^12 * busy_s and the records merge
+ * (fognet_window_stats_merge) into the merge of its node records' queue and its user records'
+ * four signals.
+ * Empty record: as the other records (counts and sums 0, every min_raw INT64_MAX, max_raw
+ * INT64_MIN). */
+typedef struct fognet_window_stats {
+    int64_t  n_publish;            /* decided publishes with arrive_tick in the window                   */
+    int64_t  n_complete;           /* completed tasks (done_tick >= 0) with done_tick in the window      */
+    uint64_t busy_lo, busy_hi;     /* node-ticks of service inside the window: the part of [start_tick,
+                                      done_tick) of every completed task that lies in it (128-bit)       */
+    uint64_t insys_lo, insys_hi;   /* task-ticks in the system inside the window: the part of [at_node,
+                                      done_tick) of every completed task, at_node = arrive + dl_k
+                                      (+ hier_up_tick where escalated), the tick it was enqueued         */
+    fognet_moments queue, delay, latency, latencyH1, taskTime;
+} fognet_window_stats;             /* 408 B, 8-B aligned */
+
+/* Window statistics of a finished replay, on the device.  in, out, user_of, U, link_stride and
+ * the links: as fognet_per_user_stats_dev; out->start_tick is needed as well.  Writes win [R][W]
+ * (device): record [r][w] covers window w over replication r's first stats[r].n_tasks publishes.
+ * n_outside [R][2] (device, nullable): the point events of replication r before t0_tick ([r][0])
+ * and at or past t0_tick + W * window_tick ([r][1]); they add to no record.  A point event is
+ * each of n_publish and n_complete and each emission of the five signals, lost ones included.
+ * Intervals are clipped and counted nowhere.
+ * A publish whose user_of lies outside [0, U) has no user-side event (delay, latency, latencyH1,
+ * taskTime); it still counts in n_publish, n_complete, busy, insys and queue, and in
+ * n_unassigned [R] (device, nullable).  With U = 0, user_of and the links may be NULL.
+ * A failed replication (status other than FOGNET_OK / FOGNET_REF_ABORTED) gets W empty records
+ * and zeros in n_outside and n_unassigned; nothing of its rows, its user_of row or its links is
+ * read (a FOGNET_REF_ABORTED one keeps its records).
+ * FOGNET_POLICY_REF_V3 and FOGNET_POLICY_EXT_LAT, with or without down_tick, the outputs of
+ * fognet_run_assigned_dev among them; FOGNET_POLICY_EXT_HIER with out->escalated (a window needs
+ * the times of an escalated task's acks, not their order inside a tick).  Refused:
+ * FOGNET_POLICY_EXT_HIER with out->escalated NULL (FOGNET_ERR_UNSUPPORTED, before anything else
+ * is checked and with nothing written); a statistics-only `out` or one without start_tick, a
+ * NULL win with R * W > 0, window_tick < 1, t0_tick < 0, W < 0, t0_tick + W * window_tick above
+ * 2^62, U < 0, a link_stride other than 0 or U, NULL links with U > 0, a NULL user_of with U > 0
+ * and R * T > 0 (FOGNET_ERR_ARG); W > FOGNET_WINDOW_MAX (FOGNET_ERR_UNSUPPORTED).  R = 0, T = 0
+ * and W = 0 succeed; W = 0 writes only n_outside and n_unassigned.
+ * The records are exact integers in any order of the updates, so two runs are byte-identical.
+ * Up to FOGNET_WINDOW_LDS_WINDOWS windows the pass needs no workspace; above, the context's
+ * workspace holds 16 B per replication and window (the cover counts of the two intervals).
+ * FOGNET_WINDOW_STATS=hbm (environment, testing): the accumulators are the caller's records and
+ * the workspace for every W, as they are above FOGNET_WINDOW_LDS_WINDOWS; the results are
+ * identical. */
+#define FOGNET_WINDOW_MAX (1 << 20)
+#ifndef FOGNET_WINDOW_LDS_WINDOWS /* (a timing build of the library may set another limit) */
+#define FOGNET_WINDOW_LDS_WINDOWS 150
+#endif
+int fognet_window_stats_dev(fognet_ctx *ctx, const fognet_batch_in *in, const fognet_batch_out *out,
+                            const int32_t *user_of, int32_t U, int32_t link_stride,
+                            const int64_t *user_ul_tick, const int64_t *user_dl_tick,
+                            int64_t t0_tick, int64_t window_tick, int32_t W,
+                            fognet_window_stats *win, int64_t *n_outside, int64_t *n_unassigned,
+                            void *hip_stream);
+/* Job reduction of the window records (device pointers): out[w] = the exact merge of win[r][w]
+ * over the replications with stats[r].status == FOGNET_OK (fognet_reduce_node_stats_dev's rule).
+ * Any R; R = 0 gives W empty records.  Needs no workspace. */
+int fognet_reduce_window_stats_dev(fognet_ctx *ctx, const fognet_window_stats *win,
+                                   const fognet_rep_stats *stats, int32_t R, int32_t W,
+                                   fognet_window_stats *out, void *hip_stream);
+/* Host-side identity (the empty record) and exact merge, field by field (ranks combine their [W]
+ * records after an all-gather). */
+void fognet_window_stats_init(fognet_window_stats *s);
+void fognet_window_stats_merge(fognet_window_stats *acc, const fognet_window_stats *other);
 
 /* Exact reduction of R per-replication stats (device pointers) into one job
  * record (device pointer).  Replications with status != OK count in n_failed

@@ -142,6 +142,24 @@ int fognet_write_vec_users(const char *path, const char *run_id, const char *net
                            const int64_t *offset, const int64_t *time, const int64_t *value,
                            const char *const *user_module, int append);
 
+/* OMNeT++ .vec vectors of a job's window records (host; fognet_window_stats_dev /
+ * fognet_reduce_window_stats_dev, fognet_hip.h): job [W], the exact merge over `replications`
+ * replications of N nodes, window w covering [t0_tick + w * window_tick, t0_tick + (w + 1) *
+ * window_tick).  Fourteen vectors with ids from id_base, "TV" columns, one row per window at
+ * the window's END time (exact decimal seconds, values %.14g):
+ *   <network>.fogNodes.udpApp[0]  utilisation:window = busy / (N * window_tick * replications),
+ *                                 tasksInSystem:window = insys / (window_tick * replications),
+ *                                 completions:window, queueTime:window(mean) (ms),
+ *                                 queueTime:window(count)
+ *   <network>.broker.udpApp[0]    publishes:window, delay:window(mean) (s), delay:window(count)
+ *   <network>.users.udpApp[0]     latency, latencyH1, taskTime: each :window(mean) (ms) and
+ *                                 :window(count)
+ * The counts are the job's totals; a mean comes from the exact sum (as fognet_write_sca's), and a
+ * window whose count is 0 has no row in a mean vector.  append: as fognet_write_vec_users. */
+int fognet_write_vec_windows(const char *path, const char *run_id, const char *network, int32_t N, int32_t W,
+                             int64_t t0_tick, int64_t window_tick, int64_t replications,
+                             const fognet_window_stats *job, int32_t id_base, int append);
+
 /* The reference task source (mqttApp2.cc:198-409 with the ini keys of
  * simulations/example/wirelessNet.ini:48-52), restated as a small event
  * simulation of U users and the broker's CONNECT handling:
