@@ -12,6 +12,7 @@ from .engine import (NEVER, BatchResult, V2Result, BrokerBaseApp2, BrokerBaseApp
                      summarize_moments, user_stats, sweep_params, node_stats, reduce_node_stats, merge_node_stats, summarize_node,
                      per_user_stats, reduce_user_stats, merge_user_stats, signal_vectors,
                      window_stats, reduce_window_stats, merge_window_stats, summarize_window,
+                     quantiles, job_quantiles, summarize_quantiles,
                      run_assigned, assign_round_robin, assign_random)
 from . import formats  # noqa: E402,F401
 
@@ -20,4 +21,5 @@ __all__ = ["Context", "BrokerBaseApp2", "BrokerBaseApp3", "BatchResult", "V2Resu
            "node_stats", "reduce_node_stats", "merge_node_stats", "summarize_node",
            "per_user_stats", "reduce_user_stats", "merge_user_stats", "signal_vectors",
            "window_stats", "reduce_window_stats", "merge_window_stats", "summarize_window",
+           "quantiles", "job_quantiles", "summarize_quantiles",
            "run_assigned", "assign_round_robin", "assign_random"]

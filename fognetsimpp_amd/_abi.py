@@ -128,6 +128,8 @@ WINDOW_HEAD = (("n_publish", C.c_int64), ("n_complete", C.c_int64), ("busy_lo", 
 WINDOW_SIGNALS = ("queue", "delay", "latency", "latencyH1", "taskTime")
 WINDOW_MAX = 1 << 20
 WINDOW_LDS_WINDOWS = 150  # FOGNET_WINDOW_LDS_WINDOWS
+QUANTILE_SIGNALS = 5  # FOGNET_QUANTILE_SIGNALS: WINDOW_SIGNALS' order
+QUANTILE_MAX = 8      # FOGNET_QUANTILE_MAX: ranks per call
 
 
 class WindowStats(C.Structure):
@@ -241,6 +243,10 @@ SIGNATURES = {
     "fognet_window_stats_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P, C.c_int32, C.c_int32, P, P,
                                           C.c_int64, C.c_int64, C.c_int32, P, P, P, P]),
     "fognet_reduce_window_stats_dev": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, P]),
+    "fognet_quantiles_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P, C.c_int32, C.c_int32, P, P,
+                                       C.POINTER(C.c_int32), C.c_int32, P, P, P, P]),
+    "fognet_job_quantiles_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P, C.c_int32, C.c_int32, P, P,
+                                           C.POINTER(C.c_int32), C.c_int32, P, P, P]),
     "fognet_window_stats_init": (None, [C.POINTER(WindowStats)]),
     "fognet_window_stats_merge": (None, [C.POINTER(WindowStats), C.POINTER(WindowStats)]),
     "fognet_user_stats_init": (None, [C.POINTER(UserStats)]),
@@ -271,6 +277,7 @@ SIGNATURES = {
                                          C.c_int]),
     "fognet_write_vec_windows": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int64,
                                            C.c_int64, C.c_int64, P, C.c_int32, C.c_int]),
+    "fognet_write_sca_quantiles": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, P, C.c_int32, P, P, P, C.c_int]),
     "fognet_gen_trace_mqtt": (C.c_int, [C.c_uint32, C.c_int32, P, P, P, P, C.c_int64, C.c_int32, C.c_int32,
                                         C.c_int32, P, P, P, C.POINTER(C.c_int32)]),
 }

@@ -982,6 +982,64 @@ int fognet_window_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fogn
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "window stats launch");
 }
 
+// fognet_quantiles_dev (job = false) and fognet_job_quantiles_dev
+static int run_quantiles(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out, const int32_t* user_of,
+                         int32_t U, int32_t link_stride, const int64_t* user_ul, const int64_t* user_dl,
+                         const int32_t* ppm, int32_t Q, int64_t* value, int64_t* count, int64_t* n_unassigned,
+                         void* stream, bool job) {
+  static const PassSpec spec = {true, false, "quantiles under EXT_HIER: an escalated task reaches its node, and sends "
+                                             "its acks, hier_up_tick later, and " FOGNET_NEEDS_ESCALATED};
+  static_assert(FOGNET_QUANTILE_MAX == 8, "the message below");
+  fognet::ReplayArgs a;
+  int rc = pass_begin(c, in, out, spec, &a);
+  if (rc) return rc;
+  if (Q < 1 || Q > FOGNET_QUANTILE_MAX) return fail(c, FOGNET_ERR_ARG, "quantiles: 1 <= Q <= 8 ranks per call");
+  for (int32_t q = 0; ppm && q < Q; ++q)
+    if (ppm[q] < 0 || ppm[q] > 1000000) return fail(c, FOGNET_ERR_ARG, "quantiles: a rank is a ppm in [0, 1000000]");
+  if (U < 0) return fail(c, FOGNET_ERR_ARG, "negative U");
+  if (link_stride != 0 && link_stride != U) return fail(c, FOGNET_ERR_ARG, "link_stride must be 0 or U");
+  if (a.R == 0 && (!job || !ppm || !value || !count)) return FOGNET_OK;
+  if (!ppm || !value || !count) return fail(c, FOGNET_ERR_ARG, "null ppm, value or count");
+  if (a.R > 0) {
+    if (!out->stats) return fail(c, FOGNET_ERR_ARG, "null stats");
+    if (!has_task_outputs(a, out, spec))
+      return fail(c, FOGNET_ERR_ARG, "quantiles need the per-task outputs, start_tick included");
+    if (U > 0 && (!user_ul || !user_dl)) return fail(c, FOGNET_ERR_ARG, "null user links");
+    if (a.T > 0 && U > 0 && !user_of) return fail(c, FOGNET_ERR_ARG, "null user_of");
+  }
+  if ((rc = pass_bind(c, out, spec, &a))) return rc;
+  // FOGNET_QUANTILES=full: no round is skipped, so small tests run both ways on the same replays
+  const bool full = env_is("FOGNET_QUANTILES", "full");
+  const fognet::UserLinks users{user_of, user_ul, user_dl, U, link_stride};
+  hipError_t e;
+  if (job) {
+    fognet::QuantWs w;
+    rc = carve(c, "job quantile counters", [&](fognet::WsCursor& v) {
+      return fognet::quantiles_ws(w, fognet::quantiles_table_count(Q), v);
+    });
+    if (rc) return rc;
+    e = fognet::launch_job_quantiles(a, users, ppm, Q, value, count, w, full, (hipStream_t)stream);
+  } else {
+    e = fognet::launch_quantiles(a, users, ppm, Q, value, count, n_unassigned, full, (hipStream_t)stream);
+  }
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "quantiles launch");
+}
+
+int fognet_quantiles_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out, const int32_t* user_of,
+                         int32_t U, int32_t link_stride, const int64_t* user_ul, const int64_t* user_dl,
+                         const int32_t* ppm, int32_t Q, int64_t* value, int64_t* count, int64_t* n_unassigned,
+                         void* stream) {
+  return run_quantiles(c, in, out, user_of, U, link_stride, user_ul, user_dl, ppm, Q, value, count, n_unassigned, stream,
+                       false);
+}
+
+int fognet_job_quantiles_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out,
+                             const int32_t* user_of, int32_t U, int32_t link_stride, const int64_t* user_ul,
+                             const int64_t* user_dl, const int32_t* ppm, int32_t Q, int64_t* value, int64_t* count,
+                             void* stream) {
+  return run_quantiles(c, in, out, user_of, U, link_stride, user_ul, user_dl, ppm, Q, value, count, nullptr, stream, true);
+}
+
 #undef FOGNET_NEEDS_ESCALATED
 
 int fognet_reduce_window_stats_dev(fognet_ctx* c, const fognet_window_stats* win, const fognet_rep_stats* stats,

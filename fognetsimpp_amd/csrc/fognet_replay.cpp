@@ -344,6 +344,7 @@ struct Options {
   uint64_t assign_seed = 0;  // --assign random:SEED
   int64_t window_tick = 0;   // --windows DT[,W]: the window length (0: no window vectors)
   int32_t windows = 0;       // ... and their number (0: ceil(stop / DT))
+  std::vector<int32_t> quantile_ppm;  // --quantiles P[,P...]: the ranks in ppm (empty: no quantiles)
   double p_busy = -1.0, p_idle = -1.0;
 };
 
@@ -491,6 +492,9 @@ void usage() {
       "                       completions, publishes and the mean and count of the five signals, over all replications\n"
       "  --user-stats         with --sca (BrokerBaseApp3 runs from an ini): append one block per user module\n"
       "                       (latency, latencyH1, taskTime) and the broker's delay\n"
+      "  --quantiles P[,P...] with --sca (BrokerBaseApp3 runs from an ini): append the exact quantiles of the five\n"
+      "                       signals over all replications, nearest rank; up to 8 percents in [0, 100] with at\n"
+      "                       most four decimals (50,99,99.9)\n"
       "  --device D           HIP device (default 0)\n"
       "  --world W --rank K --comm-id FILE   one process per GPU: rank K replays its block of the\n"
       "                       --reps replications; the job statistics are exchanged over RCCL\n"
@@ -499,6 +503,27 @@ void usage() {
       "  --dry-run            read the scenario and build the trace only (no GPU)\n"
       "  --show               print the resolved node and user parameters\n"
       "  --quiet              no summary on stdout");
+}
+
+// "99.9" -> 999000: a percent in [0, 100] with at most four decimals as ppm, digit by digit
+int32_t parse_percent(const std::string& v) {
+  const std::string what = "--quantiles: '" + v + "' ";
+  size_t i = 0;
+  int64_t whole = 0, frac = 0;
+  int decimals = 0;
+  while (i < v.size() && std::isdigit((unsigned char)v[i]) && i < 4) whole = whole * 10 + (v[i++] - '0');
+  if (i == 0) die(what + "is not a percent (digits, at most four decimals)");
+  if (i < v.size() && v[i] == '.') {
+    ++i;
+    while (i < v.size() && std::isdigit((unsigned char)v[i]) && decimals < 5) frac = frac * 10 + (v[i++] - '0'), ++decimals;
+    if (decimals == 0) die(what + "is not a percent (digits, at most four decimals)");
+    if (decimals > 4) die(what + "has more than four decimals (a rank is a whole number of ppm)");
+  }
+  if (i != v.size()) die(what + "is not a percent (digits, at most four decimals)");
+  for (; decimals < 4; ++decimals) frac *= 10;
+  const int64_t ppm = whole * 10000 + frac;
+  if (ppm > 1000000) die(what + "lies outside [0, 100]");
+  return (int32_t)ppm;
 }
 
 Options parse_args(int argc, char** argv) {
@@ -568,6 +593,19 @@ Options parse_args(int argc, char** argv) {
         o.windows = (int32_t)w;
       }
     }
+    else if (a == "--quantiles") {
+      const std::string list = need(i);
+      size_t at = 0;
+      while (true) {  // (every field counts, empty ones too: "50,,90" is malformed)
+        const size_t comma = list.find(',', at);
+        const std::string field = list.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+        if (field.empty()) die("--quantiles P[,P...]: an empty rank in '" + list + "'");
+        o.quantile_ppm.push_back(parse_percent(field));
+        if (comma == std::string::npos) break;
+        at = comma + 1;
+      }
+      if (o.quantile_ppm.size() > FOGNET_QUANTILE_MAX) die("--quantiles: at most 8 ranks per run");
+    }
     else if (a == "--world") o.world = (int)parse_int(need(i), "--world");
     else if (a == "--rank") o.rank = (int)parse_int(need(i), "--rank");
     else if (a == "--comm-id") o.comm_id = need(i);
@@ -591,6 +629,11 @@ Options parse_args(int argc, char** argv) {
   if (o.window_tick && o.world > 1) die("--windows: the window records of several ranks are not combined (--world 1)");
   if (o.window_tick && !o.trace_in.empty()) die("--windows needs the ini's user modules and stop time (-f INI)");
   if (o.window_tick && o.user_dl < 0) die("--windows needs a broker->user latency (--user-dl none gives the acks no way back)");
+  const bool quant = !o.quantile_ppm.empty();
+  if (quant && o.sca.empty()) die("--quantiles appends to the job's .sca: give --sca FILE");
+  if (quant && o.world > 1) die("--quantiles: the quantiles of several ranks cannot be merged from their records (--world 1)");
+  if (quant && !o.trace_in.empty()) die("--quantiles needs the ini's user modules (-f INI): a trace file names no users");
+  if (quant && o.user_dl < 0) die("--quantiles needs a broker->user latency (--user-dl none gives the acks no way back)");
   if (o.assign && o.policy_set) die("--assign replaces the broker's decision: not together with --policy");
   if (o.world > 1 && o.comm_id.empty()) die("--world > 1 needs --comm-id FILE (the communicator id's rendezvous)");
   if (o.reps < o.world) die("--reps must be >= --world (every rank replays a block of replications)");
@@ -903,6 +946,31 @@ void append_window_vectors(const Options& o, fognet_ctx* ctx, const DeviceBatch&
                 "\n", W, o.window_tick, merged, total[0], total[1]);
 }
 
+// --quantiles: the job's quantiles over all replications (fognet_job_quantiles_dev; links as for --user-stats),
+// appended to the .sca as one scalar per signal and rank.
+void append_quantiles(const Options& o, fognet_ctx* ctx, const DeviceBatch& db, const UserSide& us,
+                      const std::string& network, const std::string& run_id) {
+  const fognet_batch_in din = db.pass_in();
+  const fognet_batch_out dout = db.pass_out();
+  const int32_t U = (int32_t)us.modules.size(), Q = (int32_t)o.quantile_ppm.size();
+  DeviceMem mem;
+  int32_t* d_user_of = mem.copy(us.user_of);
+  int64_t* d_ul = mem.copy(std::vector<int64_t>(U, o.user_ul));
+  int64_t* d_dl = mem.copy(std::vector<int64_t>(U, o.user_dl));
+  int64_t* d_value = mem.alloc<int64_t>((size_t)FOGNET_QUANTILE_SIGNALS * Q);
+  int64_t* d_count = mem.alloc<int64_t>(FOGNET_QUANTILE_SIGNALS);
+  mem.must();
+  check_ctx(ctx, fognet_job_quantiles_dev(ctx, &din, &dout, d_user_of, U, 0, d_ul, d_dl, o.quantile_ppm.data(), Q, d_value,
+                                          d_count, nullptr),
+            "fognet_job_quantiles_dev");
+  std::vector<int64_t> value((size_t)FOGNET_QUANTILE_SIGNALS * Q), count(FOGNET_QUANTILE_SIGNALS);
+  mem.fetch(value.data(), d_value, value.size()), mem.fetch(count.data(), d_count, count.size());
+  mem.must();
+  check(fognet_write_sca_quantiles(o.sca.c_str(), run_id.c_str(), network.c_str(), nullptr, Q, o.quantile_ppm.data(),
+                                   value.data(), count.data(), 1),
+        "sca quantiles");
+}
+
 // --assign: the rule's name for the run attributes and the summary
 std::string assign_name(const Options& o) {
   return o.assign == 1 ? "rr" : "random:" + std::to_string(o.assign_seed);
@@ -990,6 +1058,7 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
   if (!o.sca.empty() && o.assign) add_run_attr(o.sca, "assign", assign_name(o));
   if (!o.sca.empty() && o.node_stats) append_node_stats(o, ctx, *db, network, run_id);
   if (!o.sca.empty() && o.user_stats && us) append_user_stats(o, ctx, *db, *us, network, run_id);
+  if (!o.sca.empty() && !o.quantile_ppm.empty() && us) append_quantiles(o, ctx, *db, *us, network, run_id);
   if (!o.vec.empty()) {  // replication 0's vectors (a failed replication has no complete outputs)
     if (stats[0].status != FOGNET_OK)
       die(std::string("--vec: replication 0 failed: ") + fognet_status_string(stats[0].status));
@@ -1149,6 +1218,8 @@ int main(int argc, char** argv) {
     die("--vec-users applies to BrokerBaseApp3 runs (the BrokerBaseApp2 model has no closed form for the user signals)");
   if (v2 && o.window_tick)
     die("--windows applies to BrokerBaseApp3 runs (the BrokerBaseApp2 replay keeps no closed form for the signals)");
+  if (v2 && !o.quantile_ppm.empty())
+    die("--quantiles applies to BrokerBaseApp3 runs (the BrokerBaseApp2 replay keeps no closed form for the signals)");
   const int32_t N = (int32_t)sc.mips.size();
   // BrokerBaseApp2 does not answer a user's CONNECT with a CONNACK, so its
   // users publish from startTime + sendInterval on
@@ -1160,7 +1231,7 @@ int main(int argc, char** argv) {
   const int r0 = o.rank * q + std::min(o.rank, rem), nr = q + (o.rank < rem ? 1 : 0);
   UserSide us;
   us.modules = sc.users;
-  const int32_t T = gen_traces(sc, o, user_dl, r0, nr, arrive, req, o.user_stats || o.vec_users || o.window_tick ? &us.user_of : nullptr);
+  const int32_t T = gen_traces(sc, o, user_dl, r0, nr, arrive, req, o.user_stats || o.vec_users || o.window_tick || !o.quantile_ppm.empty() ? &us.user_of : nullptr);
 
   // node k: CONNECT at startTime reaches the broker after ul, the CONNACK
   // comes back after dl, the first ADVERTISEMIPS fires 0.01 s later
@@ -1226,5 +1297,5 @@ int main(int argc, char** argv) {
     if (o.world > 1) die("BrokerBaseApp2 replays run on one GPU (--world 1)");
     return run_v2(o, sc, T, arrive, req, dl, ul, first_adv, run_id);
   }
-  return run_v3(o, in, sc.network, run_id, o.user_stats || o.vec_users || o.window_tick ? &us : nullptr, r0, sc.stop);
+  return run_v3(o, in, sc.network, run_id, o.user_stats || o.vec_users || o.window_tick || !o.quantile_ppm.empty() ? &us : nullptr, r0, sc.stop);
 }

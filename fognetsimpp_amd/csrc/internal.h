@@ -463,6 +463,15 @@ hipError_t launch_window_stats(const ReplayArgs& a, const UserLinks& users, int6
                                bool force_hbm, hipStream_t s);
 hipError_t launch_reduce_window_stats(const fognet_window_stats* in, const fognet_rep_stats* stats, int32_t R, int32_t W,
                                       fognet_window_stats* out, hipStream_t s);
+// Exact quantiles of the five signals (quantiles.hip): a radix select that streams the rows once
+// for the extents and once per round.  Per replication one launch and no workspace; per job one
+// row launch and one pick launch per phase over w (QuantWs; quantiles_table_count(Q) counters).
+// full: every signal starts at the first byte (no round is skipped).
+size_t quantiles_table_count(int32_t Q);
+hipError_t launch_quantiles(const ReplayArgs& a, const UserLinks& users, const int32_t* ppm, int32_t Q, int64_t* value,
+                            int64_t* count, int64_t* n_unassigned, bool full, hipStream_t s);
+hipError_t launch_job_quantiles(const ReplayArgs& a, const UserLinks& users, const int32_t* ppm, int32_t Q,
+                                int64_t* value, int64_t* count, const QuantWs& w, bool full, hipStream_t s);
 // Assigned replay (replay_assigned.hip): the node model under the caller's decisions assign [R][T],
 // a validation + count kernel and one wavefront per replication over tiles of 64 tasks.  Fills
 // a.out_node/out_status/out_start/out_done and the replay fields of a.out_stats; stats: the whole

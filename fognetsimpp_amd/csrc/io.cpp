@@ -553,6 +553,41 @@ int fognet_write_sca_users(const char* path, const char* run_id, const char* net
   return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_sca_users: write failed: ") + path);
 }
 
+// a rank in ppm as its exact percent: four decimals, trailing zeros trimmed
+static std::string percent_str(int32_t ppm) {
+  char b[32];
+  snprintf(b, sizeof b, "%d.%04d", ppm / 10000, ppm % 10000);
+  std::string s = b;
+  while (s.back() == '0') s.pop_back();
+  if (s.back() == '.') s.pop_back();
+  return s;
+}
+
+int fognet_write_sca_quantiles(const char* path, const char* run_id, const char* network, const char* const* module,
+                               int32_t Q, const int32_t* ppm, const int64_t* value, const int64_t* count, int append) {
+  if (!path || !run_id || !network || Q < 0 || (Q > 0 && (!ppm || !value)) || !count)
+    return fail(FOGNET_ERR_ARG, "write_sca_quantiles: bad argument");
+  for (int32_t q = 0; q < Q; ++q)
+    if (ppm[q] < 0 || ppm[q] > 1000000) return fail(FOGNET_ERR_ARG, "write_sca_quantiles: a rank is a ppm in [0, 1000000]");
+  static const char* const kSignal[5] = {"queueTime", "delay", "latency", "latencyH1", "taskTime"};
+  static const char* const kModule[5] = {"fogNodes", "broker", "users", "users", "users"};
+  if (module)
+    for (int s = 0; s < 5; ++s)
+      if (!module[s]) return fail(FOGNET_ERR_ARG, "write_sca_quantiles: null module name");
+  FILE* f = fopen(path, append ? "a" : "w");
+  if (!f) return fail(FOGNET_ERR_ARG, std::string("write_sca_quantiles: cannot open ") + path);
+  if (!append) run_header(f, run_id, network);
+  for (int s = 0; s < 5; ++s) {
+    if (count[s] <= 0) continue;
+    const std::string mod = module ? std::string(module[s]) : std::string(network) + "." + kModule[s] + ".udpApp[0]";
+    for (int32_t q = 0; q < Q; ++q)
+      fprintf(f, "scalar %s \t\"%s:p%s\" \t%s\n", mod.c_str(), kSignal[s], percent_str(ppm[q]).c_str(),
+              num((double)value[(size_t)s * Q + q] * 1e-12).c_str());
+  }
+  const bool ok = ferror(f) == 0;
+  return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_sca_quantiles: write failed: ") + path);
+}
+
 int fognet_write_vec(const char* path, const char* run_id, const char* network, int32_t T, int32_t N,
                      const int64_t* arrive_tick, const int64_t* dl_tick, const int32_t* node, const uint8_t* status,
                      const int64_t* start_tick, const int32_t* node_id) {

@@ -108,6 +108,22 @@ inline size_t window_stats_ws(WindowWs& w, size_t delta_n, WsCursor& v) {
   return v.off;
 }
 
+// Job quantiles (quantiles.hip): [table | state].  table: the round's [5][Q][256] 64-bit counters,
+// which every replication's workgroup adds its bins to and the pick kernel clears; state: the job's
+// select state (quantiles.hip's QState: prefixes, ranks, extents and which ranks share a histogram),
+// read by the row launches and rewritten by the pick launches between them.  Both are cleared by the
+// call's first launch, so nothing depends on what the workspace held.
+constexpr size_t kQuantStateBytes = 840;
+struct QuantWs {
+  uint64_t* table;  // [5][Q][256]
+  uint64_t* state;  // [kQuantStateBytes / 8]
+};
+
+inline size_t quantiles_ws(QuantWs& w, size_t table_n, WsCursor& v) {
+  v(w.table, table_n), v(w.state, kQuantStateBytes / 8);
+  return v.off;
+}
+
 // Assigned replay (replay_assigned.hip): [refusal flags | node offsets | advert rows || carries].
 // off: the exclusive scan of the tasks per node, one row of N + 1 per replication; adv: every
 // task's completion advert tick, grouped by node in trace order (row off[k] + rank); the five

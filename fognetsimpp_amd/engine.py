@@ -785,6 +785,87 @@ def merge_window_stats(records) -> np.ndarray:
     return np.frombuffer(bytes(acc), dtype=_abi.WINDOW_STATS_DTYPE).copy()
 
 
+def _quantile_args(trace, user_of, user_ul, user_dl, ppm):
+    """(dims, device, user tables, the ranks as a C array, Q) of the two quantile calls."""
+    dims = R, T, _, _ = _dims(trace)
+    dev = trace["arrive"].device
+    if user_of is None and user_ul is None and user_dl is None:
+        tables = (None, None, None, 0, 0)
+    else:
+        tables = _user_tables(user_of, user_ul, user_dl, R, T, dev)
+    ranks = [int(p) for p in np.asarray(ppm).reshape(-1)]
+    return dims, dev, tables, (C.c_int32 * max(len(ranks), 1))(*ranks), len(ranks)
+
+
+def _int64_out(t, shape, dev, what):
+    """The caller's int64 result tensor, checked, else a new one."""
+    if t is None:
+        return torch.empty(shape, dtype=torch.int64, device=dev)
+    if t.dtype != torch.int64 or tuple(t.shape) != tuple(shape) or t.device != dev or not t.is_contiguous():
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"{what} must be a contiguous int64 {list(shape)} tensor on the trace's "
+                                               f"device")
+    return t
+
+
+def quantiles(ctx: Context, trace: dict, out: BatchResult, user_of, user_ul, user_dl, ppm,
+              policy: str | int | None = None, hier_up_tick: int | None = None, value: torch.Tensor | None = None,
+              count: torch.Tensor | None = None, n_unassigned: torch.Tensor | None = None):
+    """Exact quantiles of the five recorded signals per replication (fognet_quantiles_dev) of a
+    finished replay on the current stream.  ``ppm``: up to ``_abi.QUANTILE_MAX`` ranks in parts per
+    million, in any order; the result for a population of n raw values is the k-th smallest,
+    k = max(1, ceil(n * ppm / 10^6)).  ``user_of`` / ``user_ul`` / ``user_dl``: as
+    :func:`window_stats`.  Returns the device tensors ``(value, count, n_unassigned)``: int64
+    [R, 5, Q] raw values in ``_abi.WINDOW_SIGNALS`` order (INT64_MAX for an empty population;
+    :func:`summarize_quantiles` gives recorded units), int64 [R, 5] population sizes and int64
+    [R] decided publishes whose user lies outside [0, U).  ``value`` / ``count`` /
+    ``n_unassigned``: write into these tensors instead of new ones.  ``policy`` and
+    ``hier_up_tick``: as for :func:`user_stats`; EXT_HIER needs ``out.escalated``."""
+    dims, dev, (uo, uu, ud, U, link_stride), ranks, Q = _quantile_args(trace, user_of, user_ul, user_dl, ppm)
+    R = dims[0]
+    value = _int64_out(value, (R, _abi.QUANTILE_SIGNALS, Q), dev, "value")
+    count = _int64_out(count, (R, _abi.QUANTILE_SIGNALS), dev, "count")
+    n_unassigned = _int64_out(n_unassigned, (R,), dev, "n_unassigned")
+    bi, bo = _pass_descriptors(trace, out, dims, _policy_of(out, policy), hier_up_tick)
+    ctx.check(ctx._lib.fognet_quantiles_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(uo), U, link_stride, _ptr(uu),
+                                            _ptr(ud), ranks, Q, _ptr(value), _ptr(count), _ptr(n_unassigned),
+                                            _stream_ptr(dev)), "quantiles")
+    return value, count, n_unassigned
+
+
+def job_quantiles(ctx: Context, trace: dict, out: BatchResult, user_of, user_ul, user_dl, ppm,
+                  policy: str | int | None = None, hier_up_tick: int | None = None, value: torch.Tensor | None = None,
+                  count: torch.Tensor | None = None):
+    """Exact quantiles of the job (fognet_job_quantiles_dev): of each signal's population pooled
+    over the replications whose status is OK.  Arguments as :func:`quantiles`.  Returns
+    ``(value, count)`` as numpy arrays, int64 [5, Q] and int64 [5]; ``value`` / ``count``: the
+    device tensors written to."""
+    dims, dev, (uo, uu, ud, U, link_stride), ranks, Q = _quantile_args(trace, user_of, user_ul, user_dl, ppm)
+    value = _int64_out(value, (_abi.QUANTILE_SIGNALS, Q), dev, "value")
+    count = _int64_out(count, (_abi.QUANTILE_SIGNALS,), dev, "count")
+    bi, bo = _pass_descriptors(trace, out, dims, _policy_of(out, policy), hier_up_tick)
+    ctx.check(ctx._lib.fognet_job_quantiles_dev(ctx.handle, C.byref(bi), C.byref(bo), _ptr(uo), U, link_stride,
+                                                _ptr(uu), _ptr(ud), ranks, Q, _ptr(value), _ptr(count),
+                                                _stream_ptr(dev)), "job_quantiles")
+    return value.cpu().numpy(), count.cpu().numpy()
+
+
+def summarize_quantiles(ppm, value, count) -> dict:
+    """Recorded units of one population set's quantiles (``value`` [5, Q] raw, ``count`` [5]), as
+    :func:`summarize_moments` gives a record's min and max: per signal a dict ``{"count": n,
+    ppm: value}`` with queueTime, latency, latencyH1 and taskTime in ms (raw * 1e-12) and delay in
+    ms from ticks (raw * 1e-9); a signal without a member has the count alone."""
+    names = ("queueTime_ms", "delay_ms", "latency_ms", "latencyH1_ms", "taskTime_ms")
+    value, count = np.asarray(value), np.asarray(count)
+    res = {}
+    for s, name in enumerate(names):
+        d = {"count": int(count[s])}
+        if d["count"]:
+            unit = 1e-9 if name == "delay_ms" else 1e-12
+            d.update({int(p): int(v) * unit for p, v in zip(np.asarray(ppm).reshape(-1), value[s])})
+        res[name] = d
+    return res
+
+
 @dataclass
 class V2Result:
     node: torch.Tensor        # [R, T] int32 (-1: served by the broker / no node)

@@ -179,6 +179,26 @@ def write_vec_windows(path: str, job, N: int, t0: int, window: int, replications
                                                 replications, _p(rec), id_base, 1 if append else 0), "write_vec_windows")
 
 
+def write_sca_quantiles(path: str, ppm, value, count, modules=None, append: bool = False,
+                        run_id: str = "General-0-fognet", network: str = "FogNet") -> None:
+    """A job's quantiles (``ppm`` [Q] ranks, ``value`` [5, Q] raw, ``count`` [5]; engine.job_quantiles)
+    as OMNeT++ `.sca` scalars ``"<signal>:p<percent>"`` in recorded units (fognet_write_sca_quantiles).
+    ``modules``: the five module paths (default: the window vectors' modules); ``append``: add the
+    lines to an existing `.sca`."""
+    ranks = np.ascontiguousarray(ppm, dtype=np.int32).reshape(-1)
+    val = np.ascontiguousarray(value, dtype=np.int64).reshape(-1)
+    cnt = np.ascontiguousarray(count, dtype=np.int64).reshape(-1)
+    if val.size != _abi.QUANTILE_SIGNALS * ranks.size or cnt.size != _abi.QUANTILE_SIGNALS:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "write_sca_quantiles: value must be [5, Q] and count [5]")
+    mods = None
+    if modules is not None:
+        if len(modules) != _abi.QUANTILE_SIGNALS:
+            raise FognetError(_abi.FOGNET_ERR_ARG, "write_sca_quantiles: five module paths")
+        mods = (C.c_char_p * _abi.QUANTILE_SIGNALS)(*(m.encode() for m in modules))
+    _check(_abi.load().fognet_write_sca_quantiles(path.encode(), run_id.encode(), network.encode(), mods, ranks.size,
+                                                  _p(ranks), _p(val), _p(cnt), 1 if append else 0), "write_sca_quantiles")
+
+
 def gen_trace_mqtt(seed: int, start, interval, uplink, downlink, stop: int, req_base: int = 200, req_span: int = 701,
                    cap: int | None = None) -> dict:
     """Reference task source (fognet_gen_trace_mqtt): per-user tick arrays

@@ -834,6 +834,65 @@ int fognet_reduce_window_stats_dev(fognet_ctx *ctx, const fognet_window_stats *w
 void fognet_window_stats_init(fognet_window_stats *s);
 void fognet_window_stats_merge(fognet_window_stats *acc, const fognet_window_stats *other);
 
+/* Quantiles.  Exact quantiles of the five recorded signals, in fognet_window_stats order: queue,
+ * delay, latency, latencyH1, taskTime.
+ * Populations.  A signal's population is the set of rows that "Signal vectors" above defines for
+ * it, under FOGNET_POLICY_EXT_HIER the emissions that fognet_window_stats_dev counts: over the
+ * replication's first stats[r].n_tasks publishes, with the same emission rule and the same links.
+ * An emission whose value leaves the simtime_t range is no member, so a population's size n is the
+ * `count` of the matching fognet_moments, not count + overflow.  A publish whose user_of lies
+ * outside [0, U) has no user-side member (delay, latency, latencyH1, taskTime); it keeps its
+ * queueTime member and counts in n_unassigned.
+ * Rank rule: nearest rank, in integers only.  A rank is asked for as ppm in [0, 1000000]; of a
+ * population of n > 0 raw values the result is the k-th smallest, k = max(1, ceil(n * ppm /
+ * 1000000)), 1-based (n * ppm stays below 2^60).  ppm = 0 is the minimum, ppm = 1000000 the
+ * maximum, and the median of four values is the second smallest.  The result is a member of the
+ * population: a raw int64 in the units of fognet_moments, never interpolated, with no floating
+ * point on the way.  For n = 0 it is INT64_MAX, the empty record's min_raw. */
+#define FOGNET_QUANTILE_SIGNALS 5
+#define FOGNET_QUANTILE_MAX 8 /* ranks per call */
+/* Quantiles per replication, on the device.  in, out, user_of, U, link_stride and the links: as
+ * fognet_window_stats_dev (with U = 0, user_of and the links may be NULL); out->start_tick is
+ * needed.  ppm [Q] (host): the ranks, which may repeat and come in any order.  Writes value
+ * [R][5][Q] (device; value[r][s][q] answers ppm[q] for signal s), count [R][5] (device; the
+ * populations' sizes) and n_unassigned [R] (device, nullable).
+ * A failed replication (status other than FOGNET_OK / FOGNET_REF_ABORTED) gets counts 0, values
+ * INT64_MAX and n_unassigned 0; nothing of its rows, its user_of row or its links is read (a
+ * FOGNET_REF_ABORTED one keeps its results).
+ * FOGNET_POLICY_REF_V3 and FOGNET_POLICY_EXT_LAT, with or without down_tick, the outputs of
+ * fognet_run_assigned_dev among them; FOGNET_POLICY_EXT_HIER with out->escalated (a quantile needs
+ * the values of an escalated task's acks, not their order inside a tick).  Refused:
+ * FOGNET_POLICY_EXT_HIER with out->escalated NULL (FOGNET_ERR_UNSUPPORTED, before anything else is
+ * checked and with nothing written); Q < 1 or Q > FOGNET_QUANTILE_MAX, a ppm outside [0, 10^6],
+ * NULL ppm, value or count with R > 0, a statistics-only `out` or one without start_tick, U < 0, a
+ * link_stride other than 0 or U, NULL links with U > 0, a NULL user_of with U > 0 and R * T > 0
+ * (FOGNET_ERR_ARG).  R = 0 and T = 0 succeed.
+ * The pass is a radix select over the key raw ^ 2^63, a byte per round, that never stores a value:
+ * every round streams the rows again.  The counts are integers in any order of the updates, so
+ * two runs are byte-identical; nothing depends on what the output buffers held, and nothing
+ * outside them is written.  Needs no workspace.
+ * FOGNET_QUANTILES=full (environment, read at the call; testing): all eight rounds run for every
+ * signal; by default the rounds of the leading bytes that a population's minimum and maximum share
+ * are skipped.  The results are identical. */
+int fognet_quantiles_dev(fognet_ctx *ctx, const fognet_batch_in *in, const fognet_batch_out *out,
+                         const int32_t *user_of, int32_t U, int32_t link_stride,
+                         const int64_t *user_ul_tick, const int64_t *user_dl_tick,
+                         const int32_t *ppm, int32_t Q, int64_t *value, int64_t *count,
+                         int64_t *n_unassigned, void *hip_stream);
+/* Quantiles of the job: of each signal's population pooled over the replications with
+ * stats[r].status == FOGNET_OK (fognet_reduce_node_stats_dev's rule: a FOGNET_REF_ABORTED or
+ * failed replication contributes nothing, and nothing of a failed one is read).  Arguments,
+ * policies and refusals as fognet_quantiles_dev; writes value [5][Q] and count [5] (device).
+ * The result is no function of the per-replication results.  R = 0 gives five empty populations.
+ * Uses the context's workspace (8 B per signal, rank and byte value, and the select's state;
+ * ordering of calls on one context: "Streams" in the Conventions above); nothing depends on what
+ * the workspace held. */
+int fognet_job_quantiles_dev(fognet_ctx *ctx, const fognet_batch_in *in, const fognet_batch_out *out,
+                             const int32_t *user_of, int32_t U, int32_t link_stride,
+                             const int64_t *user_ul_tick, const int64_t *user_dl_tick,
+                             const int32_t *ppm, int32_t Q, int64_t *value, int64_t *count,
+                             void *hip_stream);
+
 /* Exact reduction of R per-replication stats (device pointers) into one job
  * record (device pointer).  Replications with status != OK count in n_failed
  * and contribute nothing else.  R > 4096 reduces through partial records in

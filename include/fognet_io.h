@@ -160,6 +160,20 @@ int fognet_write_vec_windows(const char *path, const char *run_id, const char *n
                              int64_t t0_tick, int64_t window_tick, int64_t replications,
                              const fognet_window_stats *job, int32_t id_base, int append);
 
+/* OMNeT++ .sca scalars of a job's quantiles (host copies of fognet_job_quantiles_dev's results,
+ * fognet_hip.h "Quantiles"): ppm [Q] the ranks, value [5][Q] and count [5] in the order queue,
+ * delay, latency, latencyH1, taskTime.  One line per signal and rank, in that order,
+ *   scalar <module[s]> "<signal>:p<percent>" <value>
+ * with the signals named queueTime, delay, latency, latencyH1, taskTime, the percent printed
+ * exactly from the ppm without trailing zeros (p50, p99.9, p99.9999) and the value in the recorded
+ * units of the statistic's min / max fields (raw * 1e-12, %.14g).  A signal whose count is 0
+ * writes no line.  module: [5] module paths, nullable: fognet_write_vec_windows' modules
+ * (<network>.fogNodes.udpApp[0], <network>.broker.udpApp[0], 3 x <network>.users.udpApp[0]).
+ * append != 0: the lines are appended to an existing file without a second version/run header. */
+int fognet_write_sca_quantiles(const char *path, const char *run_id, const char *network,
+                               const char *const *module /* [5] */, int32_t Q, const int32_t *ppm,
+                               const int64_t *value /* [5][Q] */, const int64_t *count /* [5] */, int append);
+
 /* The reference task source (mqttApp2.cc:198-409 with the ini keys of
  * simulations/example/wirelessNet.ini:48-52), restated as a small event
  * simulation of U users and the broker's CONNECT handling:

@@ -7,5 +7,5 @@ cd "$(dirname "$0")/.."
 d=build/live/$1; mkdir -p $d
 S=${SRC:-fognetsimpp_amd/csrc}
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result $EXTRA -Iinclude -I$S -shared -o $d/libfognet_hip.so \
-  $S/capi.hip $S/replay.hip $S/replay_wide.hip $S/replay_v2.hip $S/replay_region.hip $S/decide.hip $S/tracegen.hip $S/user_stats.hip $S/node_stats.hip $S/per_user_stats.hip $S/signal_vectors.hip $S/replay_assigned.hip $S/window_stats.hip $S/io.cpp
+  $S/capi.hip $S/replay.hip $S/replay_wide.hip $S/replay_v2.hip $S/replay_region.hip $S/decide.hip $S/tracegen.hip $S/user_stats.hip $S/node_stats.hip $S/per_user_stats.hip $S/signal_vectors.hip $S/replay_assigned.hip $S/window_stats.hip $S/quantiles.hip $S/io.cpp
 echo built $d
