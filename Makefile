@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CXXFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
 SRC_DIR := fognetsimpp_amd/csrc
-SRCS := $(SRC_DIR)/capi.hip $(SRC_DIR)/replay.hip $(SRC_DIR)/replay_wide.hip $(SRC_DIR)/replay_v2.hip $(SRC_DIR)/replay_region.hip $(SRC_DIR)/decide.hip $(SRC_DIR)/tracegen.hip $(SRC_DIR)/user_stats.hip $(SRC_DIR)/node_stats.hip $(SRC_DIR)/per_user_stats.hip $(SRC_DIR)/signal_vectors.hip $(SRC_DIR)/replay_assigned.hip $(SRC_DIR)/window_stats.hip $(SRC_DIR)/quantiles.hip
+SRCS := $(SRC_DIR)/capi.hip $(SRC_DIR)/replay.hip $(SRC_DIR)/replay_wide.hip $(SRC_DIR)/replay_v2.hip $(SRC_DIR)/replay_region.hip $(SRC_DIR)/decide.hip $(SRC_DIR)/tracegen.hip $(SRC_DIR)/user_stats.hip $(SRC_DIR)/node_stats.hip $(SRC_DIR)/per_user_stats.hip $(SRC_DIR)/signal_vectors.hip $(SRC_DIR)/replay_assigned.hip $(SRC_DIR)/window_stats.hip $(SRC_DIR)/quantiles.hip $(SRC_DIR)/queue_stats.hip
 HDRS := include/fognet_hip.h include/fognet_io.h $(SRC_DIR)/internal.h $(SRC_DIR)/workspace.h $(SRC_DIR)/replay_common.h $(SRC_DIR)/signals.h
 OBJDIR := build/obj
 OBJS := $(patsubst $(SRC_DIR)/%.hip,$(OBJDIR)/%.o,$(SRCS)) $(OBJDIR)/io.o
@@ -79,6 +79,8 @@ asan:
 	  -o $(ASAN_DIR)/io_nodes_check
 	$(HOSTCXX) $(ASAN_FLAGS) -std=c++17 -ffp-contract=off -Iinclude tests/c/io_users_check.cpp $(SRC_DIR)/io.cpp \
 	  -o $(ASAN_DIR)/io_users_check
+	$(HOSTCXX) $(ASAN_FLAGS) -std=c++17 -ffp-contract=off -Iinclude tests/c/io_queue_check.cpp $(SRC_DIR)/io.cpp \
+	  -o $(ASAN_DIR)/io_queue_check
 	$(HOSTCXX) $(ASAN_FLAGS) -std=c++17 -ffp-contract=off -Iinclude tests/c/io_vec_users_check.cpp $(SRC_DIR)/io.cpp \
 	  -o $(ASAN_DIR)/io_vec_users_check
 	$(HOSTCXX) $(ASAN_FLAGS) -std=c++17 -ffp-contract=off -Iinclude tests/c/io_windows_check.cpp $(SRC_DIR)/io.cpp \
@@ -91,6 +93,7 @@ asan:
 	ASAN_OPTIONS=detect_leaks=1 $(ASAN_DIR)/io_check $(ASAN_DIR)
 	ASAN_OPTIONS=detect_leaks=1 $(ASAN_DIR)/io_nodes_check $(ASAN_DIR)
 	ASAN_OPTIONS=detect_leaks=1 $(ASAN_DIR)/io_users_check $(ASAN_DIR)
+	ASAN_OPTIONS=detect_leaks=1 $(ASAN_DIR)/io_queue_check $(ASAN_DIR)
 	ASAN_OPTIONS=detect_leaks=1 $(ASAN_DIR)/io_vec_users_check $(ASAN_DIR)
 	ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/io_windows_check $(ASAN_DIR)
 	ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/fognet_replay -f tests/scenarios/fog5.ini --users 'user[10]' --reps 3 \
@@ -101,6 +104,11 @@ asan:
 	! ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/fognet_replay -f tests/scenarios/fog5.ini --users 'user[2]' --ring 1000 --dry-run 2> $(ASAN_DIR)/err.txt
 	ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/fognet_replay -f tests/scenarios/fog5.ini --users 'user[4]' --reps 2 \
 	  --assign random:7 --dry-run > /dev/null
+	ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/fognet_replay -f tests/scenarios/fog5.ini --users 'user[4]' --reps 2 \
+	  --sca $(ASAN_DIR)/drv.sca --queue-stats 1,4,16 --dry-run > /dev/null
+	! ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/fognet_replay -f tests/scenarios/fog5.ini --users 'user[2]' --sca $(ASAN_DIR)/drv.sca \
+	  --queue-stats 4,2 --dry-run 2> $(ASAN_DIR)/err.txt
+	grep -q "strictly ascending" $(ASAN_DIR)/err.txt
 	! ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/fognet_replay -f tests/scenarios/fog5.ini --users 'user[2]' --assign rr \
 	  --policy EXT_LAT --dry-run 2> $(ASAN_DIR)/err.txt
 	grep -q "not together with --policy" $(ASAN_DIR)/err.txt

@@ -13,6 +13,7 @@ from .engine import (NEVER, BatchResult, V2Result, BrokerBaseApp2, BrokerBaseApp
                      per_user_stats, reduce_user_stats, merge_user_stats, signal_vectors,
                      window_stats, reduce_window_stats, merge_window_stats, summarize_window,
                      quantiles, job_quantiles, summarize_quantiles,
+                     queue_stats, reduce_queue_stats, merge_queue_stats,
                      run_assigned, assign_round_robin, assign_random)
 from . import formats  # noqa: E402,F401
 
@@ -22,4 +23,5 @@ __all__ = ["Context", "BrokerBaseApp2", "BrokerBaseApp3", "BatchResult", "V2Resu
            "per_user_stats", "reduce_user_stats", "merge_user_stats", "signal_vectors",
            "window_stats", "reduce_window_stats", "merge_window_stats", "summarize_window",
            "quantiles", "job_quantiles", "summarize_quantiles",
+           "queue_stats", "reduce_queue_stats", "merge_queue_stats",
            "run_assigned", "assign_round_robin", "assign_random"]

@@ -123,6 +123,20 @@ NODE_STATS_DTYPE = np.dtype([(n, np.int64) for n in ("n_tasks", "n_queued", "n_s
 assert NODE_STATS_DTYPE.itemsize == C.sizeof(NodeStats)
 
 
+QUEUE_LEVELS_MAX = 8  # FOGNET_QUEUE_LEVELS_MAX: levels per call
+
+
+class QueueStats(C.Structure):
+    _fields_ = [("n_enq", C.c_int64), ("max_len", C.c_int64), ("observed_lo", C.c_uint64), ("observed_hi", C.c_uint64),
+                ("area_lo", C.c_uint64), ("area_hi", C.c_uint64), ("time_ge", (C.c_uint64 * 2) * QUEUE_LEVELS_MAX)]
+
+
+QUEUE_STATS_DTYPE = np.dtype([("n_enq", np.int64), ("max_len", np.int64), ("observed_lo", np.uint64),
+                              ("observed_hi", np.uint64), ("area_lo", np.uint64), ("area_hi", np.uint64),
+                              ("time_ge", np.uint64, (QUEUE_LEVELS_MAX, 2))])
+assert QUEUE_STATS_DTYPE.itemsize == C.sizeof(QueueStats) == 176
+
+
 WINDOW_HEAD = (("n_publish", C.c_int64), ("n_complete", C.c_int64), ("busy_lo", C.c_uint64), ("busy_hi", C.c_uint64),
                ("insys_lo", C.c_uint64), ("insys_hi", C.c_uint64))
 WINDOW_SIGNALS = ("queue", "delay", "latency", "latencyH1", "taskTime")
@@ -247,6 +261,11 @@ SIGNATURES = {
                                        C.POINTER(C.c_int32), C.c_int32, P, P, P, P]),
     "fognet_job_quantiles_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), P, C.c_int32, C.c_int32, P, P,
                                            C.POINTER(C.c_int32), C.c_int32, P, P, P]),
+    "fognet_queue_stats_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), C.POINTER(C.c_int64), C.c_int32,
+                                         C.c_int64, C.c_int64, P, P]),
+    "fognet_reduce_queue_stats_dev": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, P]),
+    "fognet_queue_stats_init": (None, [C.POINTER(QueueStats)]),
+    "fognet_queue_stats_merge": (None, [C.POINTER(QueueStats), C.POINTER(QueueStats)]),
     "fognet_window_stats_init": (None, [C.POINTER(WindowStats)]),
     "fognet_window_stats_merge": (None, [C.POINTER(WindowStats), C.POINTER(WindowStats)]),
     "fognet_user_stats_init": (None, [C.POINTER(UserStats)]),
@@ -271,6 +290,7 @@ SIGNATURES = {
     "fognet_trace_read": (C.c_int, [C.c_char_p, C.POINTER(BatchIn), P]),
     "fognet_write_sca": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(JobStats), P]),
     "fognet_write_sca_nodes": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int]),
+    "fognet_write_sca_queue": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int32, P, C.c_int]),
     "fognet_write_sca_users": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int]),
     "fognet_write_vec": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P, P, P, P, P, P]),
     "fognet_write_vec_users": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P, P, P, P,

@@ -1042,6 +1042,83 @@ int fognet_job_quantiles_dev(fognet_ctx* c, const fognet_batch_in* in, const fog
 
 #undef FOGNET_NEEDS_ESCALATED
 
+// replications [r0, r0 + Rr) of a pass's argument block: every [R][..] array moved to row r0
+static fognet::ReplayArgs slice_reps(const fognet::ReplayArgs& a, int32_t r0, int32_t Rr) {
+  fognet::ReplayArgs b = a;
+  const size_t t = (size_t)r0 * (size_t)a.T, nd = (size_t)r0 * (size_t)a.node_stride;
+  b.R = Rr;
+  if (t != 0) b.arrive += t, b.req += t, b.out_node += t, b.out_status += t, b.out_start += t, b.out_done += t;
+  if (nd != 0) {
+    b.mips += nd, b.dl += nd, b.ul += nd, b.init += nd;
+    if (b.down) b.down += nd;
+  }
+  b.out_stats += r0;
+  return b;
+}
+
+int fognet_queue_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out, const int64_t* level,
+                           int32_t Q, int64_t t0, int64_t t1, fognet_queue_stats* qs, void* stream) {
+  static const PassSpec spec = {true, true, "queue-length statistics under EXT_HIER: an escalated task arrives a hop "
+                                            "later, so a node's FIFO order is no longer trace order, and where that "
+                                            "arrival stands among the events of its tick is builder-defined"};
+  static_assert(FOGNET_QUEUE_LEVELS_MAX == 8, "the message below");
+  fognet::ReplayArgs a;
+  int rc = pass_begin(c, in, out, spec, &a);
+  if (rc) return rc;
+  if (Q < 1 || Q > FOGNET_QUEUE_LEVELS_MAX) return fail(c, FOGNET_ERR_ARG, "queue statistics: 1 <= Q <= 8 levels per call");
+  if (!level) return fail(c, FOGNET_ERR_ARG, "null level");
+  for (int32_t q = 0; q < Q; ++q)
+    if (level[q] < 1 || (q > 0 && level[q] <= level[q - 1]))
+      return fail(c, FOGNET_ERR_ARG, "queue statistics: levels are >= 1 and strictly ascending");
+  if (t0 < 0 || t1 < t0 || t1 > ((int64_t)1 << 62))
+    return fail(c, FOGNET_ERR_ARG, "queue statistics: 0 <= t0_tick <= t1_tick <= 2^62");
+  if (a.R == 0) return FOGNET_OK;
+  if (!out->stats) return fail(c, FOGNET_ERR_ARG, "null stats");
+  if (!has_task_outputs(a, out, spec))
+    return fail(c, FOGNET_ERR_ARG, "queue statistics need the per-task outputs, start_tick included");
+  if (!qs) return fail(c, FOGNET_ERR_ARG, "null qs");
+  if ((rc = pass_bind(c, out, spec, &a))) return rc;
+  // FOGNET_QUEUE_STATS=hbm: counts, carries and accumulators in the workspace and the caller's records for
+  // every N (the layouts of large N), so small tests run both on the same traces
+  const bool force_hbm = env_is("FOGNET_QUEUE_STATS", "hbm");
+  const bool carry_hbm = force_hbm || a.N > fognet::queue_stats_build_lds_max();
+  // rounds: as many replications as keep a round's elements within kRoundBytes (at least one)
+  constexpr size_t kRoundBytes = (size_t)1 << 30;
+  const size_t per_rep = (size_t)a.T * fognet::kQueueElementBytes;
+  size_t round = per_rep ? kRoundBytes / per_rep : (size_t)a.R;
+  if (const char* f = getenv("FOGNET_QUEUE_ROUND")) {
+    const long v = atol(f);
+    if (v > 0) round = (size_t)v;
+  }
+  const int32_t Rr = (int32_t)(round < 1 ? 1 : round > (size_t)a.R ? (size_t)a.R : round);
+  fognet::QueueWs w;
+  rc = carve(c, "queue statistics workspace", [&](fognet::WsCursor& v) {
+    return fognet::queue_stats_ws(w, (size_t)Rr, (size_t)a.T, (size_t)a.N, carry_hbm ? (size_t)Rr * (size_t)a.N : 0, v);
+  });
+  if (rc) return rc;
+  // FOGNET_QUEUE_STAGES=1 (timing only): stop after count + build; nothing is written then
+  const int stages = env_is("FOGNET_QUEUE_STAGES", "1") ? 1 : 2;
+  for (int32_t r0 = 0; r0 < a.R; r0 += Rr) {  // (stream order: a round's kernels are done with the workspace before the next)
+    const int32_t n = a.R - r0 < Rr ? a.R - r0 : Rr;
+    const hipError_t e = fognet::launch_queue_stats(slice_reps(a, r0, n), w, level, Q, t0, t1,
+                                                    qs + (size_t)r0 * (size_t)a.N, force_hbm, stages, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(c, e, "queue statistics launch");
+  }
+  return FOGNET_OK;
+}
+
+int fognet_reduce_queue_stats_dev(fognet_ctx* c, const fognet_queue_stats* qs, const fognet_rep_stats* stats, int32_t R,
+                                  int32_t N, fognet_queue_stats* out, void* stream) {
+  if (!c) return FOGNET_ERR_ARG;
+  if (R < 0 || N < 0) return fail(c, FOGNET_ERR_ARG, "negative R/N");
+  if (N == 0) return FOGNET_OK;
+  if (!out || (R > 0 && (!qs || !stats))) return fail(c, FOGNET_ERR_ARG, "null pointer");
+  const int rc = set_device(c);
+  if (rc) return rc;
+  const hipError_t e = fognet::launch_reduce_queue_stats(qs, stats, R, N, out, (hipStream_t)stream);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "queue reduce launch");
+}
+
 int fognet_reduce_window_stats_dev(fognet_ctx* c, const fognet_window_stats* win, const fognet_rep_stats* stats,
                                    int32_t R, int32_t W, fognet_window_stats* out, void* stream) {
   if (!c) return FOGNET_ERR_ARG;
@@ -1310,6 +1387,25 @@ void fognet_window_stats_merge(fognet_window_stats* a, const fognet_window_stats
   moments_merge_host(&a->latency, &b->latency);
   moments_merge_host(&a->latencyH1, &b->latencyH1);
   moments_merge_host(&a->taskTime, &b->taskTime);
+}
+
+void fognet_queue_stats_init(fognet_queue_stats* s) {
+  if (s) memset(s, 0, sizeof *s);
+}
+
+void fognet_queue_stats_merge(fognet_queue_stats* a, const fognet_queue_stats* b) {
+  if (!a || !b) return;
+  auto add128 = [](uint64_t& lo, uint64_t& hi, uint64_t blo, uint64_t bhi) {
+    const unsigned __int128 s = (unsigned __int128)lo + blo;
+    lo = (uint64_t)s;
+    hi = hi + bhi + (uint64_t)(s >> 64);
+  };
+  a->n_enq += b->n_enq;
+  if (b->max_len > a->max_len) a->max_len = b->max_len;
+  add128(a->observed_lo, a->observed_hi, b->observed_lo, b->observed_hi);
+  add128(a->area_lo, a->area_hi, b->area_lo, b->area_hi);
+  for (int q = 0; q < FOGNET_QUEUE_LEVELS_MAX; ++q)
+    add128(a->time_ge[q][0], a->time_ge[q][1], b->time_ge[q][0], b->time_ge[q][1]);
 }
 
 int fognet_gen_trace_dev(fognet_ctx* c, const fognet_gen_params* p, int64_t r0, int32_t R, int32_t T, int32_t N,

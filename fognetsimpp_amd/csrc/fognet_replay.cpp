@@ -345,6 +345,7 @@ struct Options {
   int64_t window_tick = 0;   // --windows DT[,W]: the window length (0: no window vectors)
   int32_t windows = 0;       // ... and their number (0: ceil(stop / DT))
   std::vector<int32_t> quantile_ppm;  // --quantiles P[,P...]: the ranks in ppm (empty: no quantiles)
+  std::vector<int64_t> queue_levels;  // --queue-stats [L1,L2,...]: the queue lengths (empty: no queue statistics)
   double p_busy = -1.0, p_idle = -1.0;
 };
 
@@ -495,6 +496,9 @@ void usage() {
       "  --quantiles P[,P...] with --sca (BrokerBaseApp3 runs from an ini): append the exact quantiles of the five\n"
       "                       signals over all replications, nearest rank; up to 8 percents in [0, 100] with at\n"
       "                       most four decimals (50,99,99.9)\n"
+      "  --queue-stats [L,...]  with --sca (BrokerBaseApp3 runs): append to every fog node's block the longest queue,\n"
+      "                       its enqueues, its time average and the share of the run with L or more tasks\n"
+      "                       waiting, for up to 8 ascending lengths (default 1,2,4,8,16,32,64,128)\n"
       "  --device D           HIP device (default 0)\n"
       "  --world W --rank K --comm-id FILE   one process per GPU: rank K replays its block of the\n"
       "                       --reps replications; the job statistics are exchanged over RCCL\n"
@@ -606,6 +610,20 @@ Options parse_args(int argc, char** argv) {
       }
       if (o.quantile_ppm.size() > FOGNET_QUANTILE_MAX) die("--quantiles: at most 8 ranks per run");
     }
+    else if (a == "--queue-stats") {
+      // the list is optional: the next argument is taken as one when it starts with a digit
+      std::string list = "1,2,4,8,16,32,64,128";
+      if (i + 1 < argc && std::isdigit((unsigned char)argv[i + 1][0])) list = argv[++i];
+      o.queue_levels.clear();
+      for (const std::string& f : split(list, ',')) {
+        const long long l = parse_int(f, "--queue-stats L[,L...]");
+        if (l < 1) die("--queue-stats: a level is a queue length >= 1");
+        if (!o.queue_levels.empty() && l <= o.queue_levels.back()) die("--queue-stats: the levels must be strictly ascending");
+        o.queue_levels.push_back(l);
+      }
+      if (o.queue_levels.empty() || o.queue_levels.size() > FOGNET_QUEUE_LEVELS_MAX)
+        die("--queue-stats: 1 to 8 levels per run");
+    }
     else if (a == "--world") o.world = (int)parse_int(need(i), "--world");
     else if (a == "--rank") o.rank = (int)parse_int(need(i), "--rank");
     else if (a == "--comm-id") o.comm_id = need(i);
@@ -634,6 +652,9 @@ Options parse_args(int argc, char** argv) {
   if (quant && o.world > 1) die("--quantiles: the quantiles of several ranks cannot be merged from their records (--world 1)");
   if (quant && !o.trace_in.empty()) die("--quantiles needs the ini's user modules (-f INI): a trace file names no users");
   if (quant && o.user_dl < 0) die("--quantiles needs a broker->user latency (--user-dl none gives the acks no way back)");
+  if (!o.queue_levels.empty() && o.sca.empty()) die("--queue-stats appends to the job's .sca: give --sca FILE");
+  if (!o.queue_levels.empty() && o.world > 1)
+    die("--queue-stats: the per-node records of several ranks are not combined (--world 1)");
   if (o.assign && o.policy_set) die("--assign replaces the broker's decision: not together with --policy");
   if (o.world > 1 && o.comm_id.empty()) die("--world > 1 needs --comm-id FILE (the communicator id's rendezvous)");
   if (o.reps < o.world) die("--reps must be >= --world (every rank replays a block of replications)");
@@ -819,6 +840,31 @@ void append_node_stats(const Options& o, fognet_ctx* ctx, const DeviceBatch& db,
   mem.fetch(nodes.data(), d_job, N);
   mem.must();
   check(fognet_write_sca_nodes(o.sca.c_str(), run_id.c_str(), network.c_str(), din.N, nodes.data(), nullptr, 1), "sca nodes");
+}
+
+// --queue-stats: the queue records (fognet_queue_stats_dev) over [0, the job's last tick + 1), reduced over
+// the replications (fognet_reduce_queue_stats_dev): scalars appended to every fog node's module block.
+void append_queue_stats(const Options& o, fognet_ctx* ctx, const DeviceBatch& db, const std::string& network,
+                        const std::string& run_id, int64_t last_tick) {
+  const fognet_batch_in din = db.pass_in();
+  const fognet_batch_out dout = db.pass_out();
+  const size_t R = (size_t)din.R, N = (size_t)din.N;
+  const int32_t Q = (int32_t)o.queue_levels.size();
+  DeviceMem mem;
+  fognet_queue_stats* d_qs = mem.alloc<fognet_queue_stats>(R * N);
+  fognet_queue_stats* d_job = mem.alloc<fognet_queue_stats>(N);
+  mem.must();
+  check_ctx(ctx, fognet_queue_stats_dev(ctx, &din, &dout, o.queue_levels.data(), Q, 0, last_tick < 0 ? 0 : last_tick + 1,
+                                        d_qs, nullptr),
+            "fognet_queue_stats_dev");
+  check_ctx(ctx, fognet_reduce_queue_stats_dev(ctx, d_qs, dout.stats, din.R, din.N, d_job, nullptr),
+            "fognet_reduce_queue_stats_dev");
+  std::vector<fognet_queue_stats> qs(N);
+  mem.fetch(qs.data(), d_job, N);
+  mem.must();
+  check(fognet_write_sca_queue(o.sca.c_str(), run_id.c_str(), network.c_str(), din.N, qs.data(), o.queue_levels.data(), Q,
+                               nullptr, 1),
+        "sca queue");
 }
 
 // what --user-stats adds to a BrokerBaseApp3 run: the users in --users order and every publish's user
@@ -1057,6 +1103,7 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
   if (!o.sca.empty()) check(fognet_write_sca(o.sca.c_str(), run_id.c_str(), network.c_str(), &job, hist.data()), "sca");
   if (!o.sca.empty() && o.assign) add_run_attr(o.sca, "assign", assign_name(o));
   if (!o.sca.empty() && o.node_stats) append_node_stats(o, ctx, *db, network, run_id);
+  if (!o.sca.empty() && !o.queue_levels.empty()) append_queue_stats(o, ctx, *db, network, run_id, job.last_tick);
   if (!o.sca.empty() && o.user_stats && us) append_user_stats(o, ctx, *db, *us, network, run_id);
   if (!o.sca.empty() && !o.quantile_ppm.empty() && us) append_quantiles(o, ctx, *db, *us, network, run_id);
   if (!o.vec.empty()) {  // replication 0's vectors (a failed replication has no complete outputs)
@@ -1212,6 +1259,8 @@ int main(int argc, char** argv) {
     die("broker module " + sc.broker_type + " is not on the engine's path (BrokerBaseApp3, BrokerBaseApp2)");
   if (v2 && o.policy_set) die("--policy applies to BrokerBaseApp3 runs");
   if (v2 && o.assign) die("--assign applies to BrokerBaseApp3 runs (the BrokerBaseApp2 broker serves tasks itself)");
+  if (v2 && !o.queue_levels.empty())
+    die("--queue-stats applies to BrokerBaseApp3 runs (the BrokerBaseApp2 nodes keep no requests vector)");
   if (v2 && o.user_stats)
     die("--user-stats applies to BrokerBaseApp3 runs (the BrokerBaseApp2 model has no closed form for the user signals)");
   if (v2 && o.vec_users)

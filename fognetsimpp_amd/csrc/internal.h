@@ -481,6 +481,18 @@ hipError_t launch_job_quantiles(const ReplayArgs& a, const UserLinks& users, con
 int32_t replay_assigned_lds_max();
 hipError_t launch_replay_assigned(const ReplayArgs& a, const int32_t* assign, const AssignedWs& w, bool stats,
                                   bool force_hbm, int stages, hipStream_t s);
+// Queue-length statistics of a finished replay and their job reduction (queue_stats.hip): count,
+// build, measure over the replications of a (one round's slice of the job).  Up to
+// queue_stats_lds_max() nodes the records live in LDS, up to queue_stats_build_lds_max() nodes the
+// build kernel's carries, unless force_hbm; w: the workspace (QueueWs).  level [Q] (host): validated
+// by the caller.  stages: 1 stops after count + build (timing), 2: the whole pass.  The reduction is
+// one workgroup per node over any R and needs no workspace.
+int32_t queue_stats_lds_max();
+int32_t queue_stats_build_lds_max();
+hipError_t launch_queue_stats(const ReplayArgs& a, const QueueWs& w, const int64_t* level, int32_t Q, int64_t t0,
+                              int64_t t1, fognet_queue_stats* out, bool force_hbm, int stages, hipStream_t s);
+hipError_t launch_reduce_queue_stats(const fognet_queue_stats* in, const fognet_rep_stats* stats, int32_t R, int32_t N,
+                                     fognet_queue_stats* out, hipStream_t s);
 // v2 model replay (replay_v2.hip)
 size_t replay_v2_workspace_bytes(int32_t R, int32_t T, int32_t N, int32_t q_log2);
 hipError_t launch_replay_v2(const fognet_v2_in& in, const fognet_v2_out& out, void* workspace, int32_t q_log2,

@@ -502,6 +502,34 @@ int fognet_write_sca_nodes(const char* path, const char* run_id, const char* net
   return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_sca_nodes: write failed: ") + path);
 }
 
+// a 128-bit tick count (lo, hi) as a floating-point value
+static long double ticks128(uint64_t lo, uint64_t hi) { return (long double)hi * 18446744073709551616.0L + (long double)lo; }
+
+int fognet_write_sca_queue(const char* path, const char* run_id, const char* network, int32_t N,
+                           const fognet_queue_stats* qs, const int64_t* level, int32_t Q, const int32_t* node_id,
+                           int append) {
+  if (!path || !run_id || !network || N < 0 || (N > 0 && !qs) || Q < 0 || Q > FOGNET_QUEUE_LEVELS_MAX || (Q > 0 && !level))
+    return fail(FOGNET_ERR_ARG, "write_sca_queue: bad argument");
+  FILE* f = fopen(path, append ? "a" : "w");
+  if (!f) return fail(FOGNET_ERR_ARG, std::string("write_sca_queue: cannot open ") + path);
+  if (!append) run_header(f, run_id, network);
+  for (int32_t j = 0; j < N; ++j) {
+    const fognet_queue_stats& s = qs[j];
+    const std::string mod = std::string(network) + ".fogNode[" + std::to_string(node_id ? node_id[j] : j) + "].udpApp[0]";
+    const long double observed = ticks128(s.observed_lo, s.observed_hi);
+    // a share of the observed time (0 / 0: nothing was observed)
+    auto share = [&](uint64_t lo, uint64_t hi) { return num((double)(ticks128(lo, hi) / observed)); };
+    fprintf(f, "scalar %s \tqueueLength:max \t%lld\n", mod.c_str(), (long long)s.max_len);
+    fprintf(f, "scalar %s \tqueueLength:enqueued \t%lld\n", mod.c_str(), (long long)s.n_enq);
+    fprintf(f, "scalar %s \tqueueLength:timeavg \t%s\n", mod.c_str(), share(s.area_lo, s.area_hi).c_str());
+    for (int32_t q = 0; q < Q; ++q)
+      fprintf(f, "scalar %s \tqueueLength:ge%lld \t%s\n", mod.c_str(), (long long)level[q],
+              share(s.time_ge[q][0], s.time_ge[q][1]).c_str());
+  }
+  const bool ok = ferror(f) == 0;
+  return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_sca_queue: write failed: ") + path);
+}
+
 // one fognet_moments of raw emitted values as a .sca statistic (recorded value raw * 1e-12)
 static void moments_statistic(FILE* f, const std::string& mod, const char* name, const fognet_moments& m) {
   // the 128-bit two's complement sum, sign-extended to the 192 bits moments() takes
@@ -701,7 +729,6 @@ int fognet_write_vec_windows(const char* path, const char* run_id, const char* n
       if (!s.empty()) fprintf(f, "%lld\t%s\t%s\n", v, end_of(w).c_str(), s.c_str());
     }
   };
-  auto ticks128 = [](uint64_t lo, uint64_t hi) { return (long double)hi * 18446744073709551616.0L + (long double)lo; };
   auto count = [](int64_t n) { return std::to_string((long long)n); };
   // the mean of the raw values from their exact sum (recorded value raw * 1e-12: ms, delay s)
   auto mean = [](const fognet_moments& m) {

@@ -144,4 +144,29 @@ inline size_t assigned_ws(AssignedWs& w, size_t R, size_t T, size_t N, size_t ca
   return v.off;
 }
 
+// Queue-length statistics (queue_stats.hip): [node offsets | elements || carries].  off: the
+// exclusive scan of the queued tasks per node, one row of N + 1 per replication; the elements of a
+// replication (at most T: its queued tasks) are four columns grouped by node in FIFO order (row
+// off[k] + rank): the tick the task was enqueued, the tick it left, the start of the task served
+// before it, and its node; the two carry arrays hold what a node carries from tile to tile of the
+// build kernel where it does not fit in LDS (carry_n = R * N above that kernel's LDS capacity or
+// when the workspace layout is forced, else 0).  R: the replications of one round.
+struct QueueWs {
+  uint32_t* off;     // [R][N + 1]
+  int64_t* at;       // [R][T]
+  int64_t* leave;    // [R][T]
+  int64_t* prev;     // [R][T]
+  int32_t* node;     // [R][T]
+  int64_t* c_start;  // [R][N] the carries (queue_stats.hip says what each holds)
+  uint32_t* c_rank;
+};
+
+constexpr size_t kQueueElementBytes = 28;
+
+inline size_t queue_stats_ws(QueueWs& w, size_t R, size_t T, size_t N, size_t carry_n, WsCursor& v) {
+  v(w.off, R * (N + 1)), v(w.at, R * T), v(w.leave, R * T), v(w.prev, R * T), v(w.node, R * T);
+  v(w.c_start, carry_n), v(w.c_rank, carry_n);
+  return v.off;
+}
+
 }  // namespace fognet

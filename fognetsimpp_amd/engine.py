@@ -604,6 +604,70 @@ def merge_node_stats(records) -> np.ndarray:
     return np.frombuffer(bytes(acc), dtype=_abi.NODE_STATS_DTYPE).copy()
 
 
+QUEUE_LEVELS = (1, 2, 4, 8, 16, 32, 64, 128)
+
+
+def queue_stats(ctx: Context, trace: dict, out: BatchResult, levels=QUEUE_LEVELS, t0_tick: int = 0,
+                t1_tick: int | None = None, policy: str | int | None = None,
+                res: torch.Tensor | None = None) -> torch.Tensor:
+    """Queue-length statistics (fognet_queue_stats_dev) of a finished replay on the current
+    stream: per fog node the longest ``requests`` vector, its time integral and the ticks it held
+    each of ``levels`` (1 to 8 strictly ascending lengths >= 1) or more, over the ticks
+    [``t0_tick``, ``t1_tick``).  ``t1_tick`` None: one past the latest ``last_tick`` of the
+    replications' records, which covers every replication whole (this reads the records back).
+    Returns the device buffer of the records, uint8 [R, N * sizeof(fognet_queue_stats)]
+    (``.cpu().numpy().view(_abi.QUEUE_STATS_DTYPE)`` gives [R, N] records); ``res``: write into this
+    buffer instead of a new one.  ``policy``: the replay's ("REF_V3" or "EXT_LAT", the outputs of
+    :func:`run_assigned` among them; None takes the one recorded on ``out``); "EXT_HIER" is refused
+    (FOGNET_ERR_UNSUPPORTED).  A failed replication gets all-zero records."""
+    dims = R, _, N, _ = _dims(trace)
+    dev = trace["arrive"].device
+    lv = [int(x) for x in levels]
+    if t1_tick is None:
+        st = out.rep_stats()
+        ok = st["last_tick"][np.isin(st["status"], (_abi.FOGNET_OK, _abi.FOGNET_REF_ABORTED))] if R else np.zeros(0)
+        t1_tick = max(int(ok.max()) + 1, int(t0_tick)) if ok.size and int(ok.max()) >= 0 else int(t0_tick)
+    nres = R * N * _abi.QUEUE_STATS_DTYPE.itemsize
+    res = _record_buffer(res, nres, dev, "res")
+    pol = _policy_of(out, policy)
+    bi = _batch_in(trace, *dims, pol, down=True, region=pol == _abi.FOGNET_POLICY_EXT_HIER)
+    bo = _batch_out(out)
+    arr = (C.c_int64 * max(len(lv), 1))(*lv)
+    ctx.check(ctx._lib.fognet_queue_stats_dev(ctx.handle, C.byref(bi), C.byref(bo), arr, len(lv), int(t0_tick),
+                                              int(t1_tick), _ptr(res), _stream_ptr(dev)), "queue_stats")
+    return res[:nres].view(R, N * _abi.QUEUE_STATS_DTYPE.itemsize)
+
+
+def reduce_queue_stats(ctx: Context, queue_stats: torch.Tensor, stats: torch.Tensor, R: int, N: int,
+                       out: torch.Tensor | None = None) -> np.ndarray:
+    """Exact job reduction of queue records on the device (fognet_reduce_queue_stats_dev): record k
+    merges node k over the replications whose status is OK (sums, and the maximum of max_len).
+    ``queue_stats``: :func:`queue_stats`'s buffer; ``stats``: the replications' records
+    (BatchResult.stats).  Returns QUEUE_STATS_DTYPE [N]; ``out``: the device buffer written to."""
+    nout = N * _abi.QUEUE_STATS_DTYPE.itemsize
+    dev = stats.device
+    out = _record_buffer(out, nout, dev, "out", alloc=max(nout, 1))
+    if queue_stats.numel() < R * nout or stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "queue_stats / stats smaller than R replications")
+    ctx.check(ctx._lib.fognet_reduce_queue_stats_dev(ctx.handle, _ptr(queue_stats), _ptr(stats), R, N, _ptr(out),
+                                                     _stream_ptr(dev)), "reduce_queue_stats")
+    return out[:nout].cpu().numpy().view(_abi.QUEUE_STATS_DTYPE)
+
+
+def merge_queue_stats(records) -> np.ndarray:
+    """Exact host merge of queue record arrays [N] (fognet_queue_stats_merge) into one [N]."""
+    lib = _abi.load()
+    records = [np.ascontiguousarray(r, dtype=_abi.QUEUE_STATS_DTYPE).reshape(-1) for r in records]
+    N = records[0].size if records else 0
+    acc = (_abi.QueueStats * N)()
+    for j in range(N):
+        lib.fognet_queue_stats_init(C.byref(acc[j]))
+        for rec in records:
+            b = _abi.QueueStats.from_buffer_copy(rec[j].tobytes())
+            lib.fognet_queue_stats_merge(C.byref(acc[j]), C.byref(b))
+    return np.frombuffer(bytes(acc), dtype=_abi.QUEUE_STATS_DTYPE).copy()
+
+
 def per_user_stats(ctx: Context, trace: dict, out: BatchResult, user_of, user_ul, user_dl,
                    policy: str | int | None = None, res: torch.Tensor | None = None,
                    hier_up_tick: int | None = None, allow_unassigned: bool = False,

@@ -111,6 +111,21 @@ def write_sca_nodes(path: str, nodes, node_id=None, append: bool = False, run_id
                                               _p(nid), 1 if append else 0), "write_sca_nodes")
 
 
+def write_sca_queue(path: str, queue, levels, node_id=None, append: bool = False, run_id: str = "General-0-fognet",
+                    network: str = "FogNet") -> None:
+    """Per-node queue scalars of QUEUE_STATS_DTYPE records [N] (fognet_write_sca_queue) under
+    <network>.fogNode[<node_id or index>].udpApp[0]: queueLength:max, :enqueued, :timeavg and one
+    :ge<level> per entry of ``levels`` (the levels of the call that made the records).  ``append``:
+    add them to the file :func:`write_sca` wrote instead of starting a new one."""
+    rec = np.ascontiguousarray(queue, dtype=_abi.QUEUE_STATS_DTYPE).reshape(-1)
+    lv = np.ascontiguousarray(levels, dtype=np.int64).reshape(-1)
+    nid = np.ascontiguousarray(node_id, dtype=np.int32).reshape(-1) if node_id is not None else None
+    if nid is not None and nid.size != rec.size:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "write_sca_queue: node_id length differs from the records'")
+    _check(_abi.load().fognet_write_sca_queue(path.encode(), run_id.encode(), network.encode(), rec.size, _p(rec),
+                                              _p(lv), lv.size, _p(nid), 1 if append else 0), "write_sca_queue")
+
+
 def write_sca_users(path: str, users, user_module=None, append: bool = False, run_id: str = "General-0-fognet",
                     network: str = "FogNet") -> None:
     """Per-user `.sca` blocks of USER_STATS_DTYPE records [U] (fognet_write_sca_users):

@@ -893,6 +893,69 @@ int fognet_job_quantiles_dev(fognet_ctx *ctx, const fognet_batch_in *in, const f
                              const int32_t *ppm, int32_t Q, int64_t *value, int64_t *count,
                              void *hip_stream);
 
+/* Queue-length statistics.  For fog node k of replication r, L(t) is the length of its `requests`
+ * vector (ComputeBrokerApp3.cc:309 push_back, :246 erase): the tasks waiting, the one in service
+ * not among them.
+ * A decided task enters the queue when it reaches its node, at_node = arrive_tick + dl_k, and is
+ * answered status 4; it leaves at its start_tick.  A status-5 or status-9 task never enters.  Under
+ * down_tick a queued task that never starts (start_tick = -1) leaves at down_tick[k]; the crash
+ * precedes every model event of its tick, so such a task takes part in no tie.
+ * Same-tick order (it changes only the maximum): the FES order of DESIGN.md §3.3.  Take the dequeue
+ * at tick x caused by the completion of the task served just before it, which started at
+ * prev_start, and an enqueue at tick x of a publish that reached the broker at t = x - dl_k.  The
+ * enqueue comes first iff t <= prev_start: the arrival event was then inserted no later than the
+ * RELEASERESOURCE timer, and at equal insertion ticks the pre-inserted publish ran first.
+ * A call observes the ticks [t0_tick, t1_tick) and takes up to FOGNET_QUEUE_LEVELS_MAX strictly
+ * ascending levels level[q] >= 1.  The empty record, given to a failed replication, is all zero.
+ * Everything is an exact integer in any order of the updates, so two runs are byte-identical. */
+#define FOGNET_QUEUE_LEVELS_MAX 8
+typedef struct fognet_queue_stats {
+    int64_t  n_enq;       /* enqueues with t0 <= at_node < t1                                  */
+    int64_t  max_len;     /* largest L right after one of those enqueues (0: none).  A length
+                             carried into the range from before t0 is no enqueue of the range. */
+    uint64_t observed_lo, observed_hi;  /* t1 - t0 of every replication merged into the record */
+    uint64_t area_lo, area_hi;          /* integral of L over the range: the part of [at_node,
+                                           leave) of every queued task that lies in it         */
+    uint64_t time_ge[FOGNET_QUEUE_LEVELS_MAX][2]; /* ticks of the range with L >= level[q]
+                                                     (lo, hi); q >= Q: 0                       */
+} fognet_queue_stats;                   /* 176 B, 8-B aligned */
+
+/* Queue-length statistics of a finished replay, on the device.  in (arrive_tick, dl_tick,
+ * down_tick) and out (node, status, start_tick, stats[r].{n_tasks,status}): device pointers, as
+ * fognet_node_stats_dev.  level [Q] (host).  Writes qs [R][N] (device): record [r][k] covers node k
+ * over replication r's first stats[r].n_tasks publishes.
+ * A failed replication (status other than FOGNET_OK / FOGNET_REF_ABORTED) gets N empty records and
+ * none of its rows is read (a FOGNET_REF_ABORTED one keeps its records).
+ * FOGNET_POLICY_REF_V3 and FOGNET_POLICY_EXT_LAT, with or without down_tick, the outputs of
+ * fognet_run_assigned_dev among them.  Refused, before anything is written:
+ * FOGNET_POLICY_EXT_HIER, with or without out->escalated (FOGNET_ERR_UNSUPPORTED: an escalated task
+ * arrives a hop later, so a node's FIFO order is no longer trace order, and the place of that
+ * arrival within its tick is the unpinned order that keeps the signal vectors from EXT_HIER); a
+ * statistics-only `out` or one without start_tick, Q < 1 or Q > FOGNET_QUEUE_LEVELS_MAX, a level
+ * below 1 or levels not strictly ascending, t0_tick < 0, t1_tick < t0_tick, t1_tick > 2^62, NULL
+ * level, NULL qs with R * N > 0 (FOGNET_ERR_ARG).  R = 0, T = 0 and t1_tick = t0_tick succeed.
+ * Uses the context's workspace (28 B per task, 4 B per replication and node; 12 B more per
+ * replication and node above 2,048 nodes); a job whose elements pass 1 GiB runs its replications in
+ * rounds (ordering of calls on one context: "Streams" in the Conventions above).  Nothing depends
+ * on what the workspace or qs held.
+ * FOGNET_QUEUE_STATS=hbm (environment, testing): the counts, carries and accumulators live in the
+ * workspace and the caller's records for every N, as they do above 256 nodes (records), 2,048
+ * (carries) and 8,192 (counts); the results are identical.  FOGNET_QUEUE_ROUND=<n> (testing): n
+ * replications per round.  FOGNET_QUEUE_STAGES=1 (timing only): stop before the measure kernel; no
+ * output is written then. */
+int fognet_queue_stats_dev(fognet_ctx *ctx, const fognet_batch_in *in, const fognet_batch_out *out,
+                           const int64_t *level, int32_t Q, int64_t t0_tick, int64_t t1_tick,
+                           fognet_queue_stats *qs, void *hip_stream);
+/* Job reduction of the queue records (device pointers): out[k] = the exact merge of qs[r][k] over
+ * the replications with stats[r].status == FOGNET_OK (fognet_reduce_node_stats_dev's rule): sums,
+ * and the maximum of max_len.  Any R; R = 0 gives N empty records.  Needs no workspace. */
+int fognet_reduce_queue_stats_dev(fognet_ctx *ctx, const fognet_queue_stats *qs,
+                                  const fognet_rep_stats *stats, int32_t R, int32_t N,
+                                  fognet_queue_stats *out, void *hip_stream);
+/* Host-side identity (the empty record) and exact merge. */
+void fognet_queue_stats_init(fognet_queue_stats *s);
+void fognet_queue_stats_merge(fognet_queue_stats *acc, const fognet_queue_stats *other);
+
 /* Exact reduction of R per-replication stats (device pointers) into one job
  * record (device pointer).  Replications with status != OK count in n_failed
  * and contribute nothing else.  R > 4096 reduces through partial records in

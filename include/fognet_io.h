@@ -99,6 +99,18 @@ int fognet_write_sca(const char *path, const char *run_id, const char *network, 
 int fognet_write_sca_nodes(const char *path, const char *run_id, const char *network, int32_t N,
                            const fognet_node_stats *nodes, const int32_t *node_id, int append);
 
+/* OMNeT++ .sca scalars of per-node queue records (host; fognet_queue_stats_dev /
+ * fognet_reduce_queue_stats_dev, fognet_hip.h "Queue-length statistics"): qs [N], level [Q] the
+ * levels of the call that made them.  Per module <network>.fogNode[<node_id or index>].udpApp[0]
+ * (fognet_write_sca_nodes' naming, so the lines join that block) the scalars
+ *   queueLength:max, queueLength:enqueued, queueLength:timeavg = area / observed, and per level
+ *   queueLength:ge<level> = time_ge / observed,
+ * the counts as integers, the shares %.14g from the 128-bit sums (-nan where observed is 0).
+ * append and node_id: as fognet_write_sca_nodes. */
+int fognet_write_sca_queue(const char *path, const char *run_id, const char *network, int32_t N,
+                           const fognet_queue_stats *qs, const int64_t *level, int32_t Q,
+                           const int32_t *node_id, int append);
+
 /* OMNeT++ .sca blocks of per-user records (host; fognet_per_user_stats_dev /
  * fognet_reduce_user_stats_dev, fognet_hip.h): per module
  * <network>.<user_module[u] or "user[u]">.udpApp[0] the statistics `latency:stats`,
