@@ -641,9 +641,22 @@ __device__ __forceinline__ void fused_stats_epilogue(const ReplayArgs& A, int r,
   ab_t[lane] = INT64_MAX;
   ab_k[lane] = INT32_MAX;
   __syncthreads();
+  const auto dl_of = [&](int k) { return s_dl[k]; };
   if (from_tails) {
-    stats_accumulate_packed<4, false>(A, tbase, (int)n_done, lane, write_back, acc, e_busy, e_hist,
-                                      [&](int k) { return s_dl[k]; }, ab_t, ab_k);
+    // the pass of every completed replay: one instantiation per flag pair, no flag test in a row
+    const bool hist = A.hist != nullptr;
+    if (hist && write_back)
+      stats_accumulate_packed<4, false, true, true, true>(A, tbase, (int)n_done, lane, true, acc, e_busy, e_hist,
+                                                          dl_of, ab_t, ab_k);
+    else if (hist)
+      stats_accumulate_packed<4, false, true, true, false>(A, tbase, (int)n_done, lane, false, acc, e_busy, e_hist,
+                                                           dl_of, ab_t, ab_k);
+    else if (write_back)
+      stats_accumulate_packed<4, false, true, false, true>(A, tbase, (int)n_done, lane, true, acc, e_busy, e_hist,
+                                                           dl_of, ab_t, ab_k);
+    else
+      stats_accumulate_packed<4, false, true, false, false>(A, tbase, (int)n_done, lane, false, acc, e_busy, e_hist,
+                                                            dl_of, ab_t, ab_k);
     // (after the pass, which touches neither the tails nor e_busy here: its
     // loop then carries no busy and `last` accumulators)
     for (int j = lane; j < NPL * kWave; j += kWave) {
@@ -654,8 +667,8 @@ __device__ __forceinline__ void fused_stats_epilogue(const ReplayArgs& A, int r,
       if (A.p_busy) e_busy[j] = B;  // aliases s_tld[j]: read above by this lane
     }
   } else {
-    stats_accumulate_packed<4, true>(A, tbase, (int)n_done, lane, write_back, acc, e_busy, e_hist,
-                                     [&](int k) { return s_dl[k]; }, ab_t, ab_k);
+    stats_accumulate_packed<4, true, false, false, false>(A, tbase, (int)n_done, lane, write_back, acc, e_busy,
+                                                          e_hist, dl_of, ab_t, ab_k);
   }
   const AbortPt ab = wave_min_abort(AbortPt{ab_t[lane], ab_k[lane]});  // (each lane's own slot)
   acc = wave_merge(acc);
@@ -711,6 +724,9 @@ __device__ __forceinline__ void replay_body(const ReplayArgs& A, const int r, co
   __shared__ uint8_t s_os[kBufOut ? kWave : 1];
   __shared__ uint8_t s_oS[kBufOut ? kWave : 1];
   __shared__ int64_t s_od[kBufOut ? kWave : 1];
+  // ... and the replication's rows of the four output arrays (base + r * T), formed once: the flush
+  // reads them with the chunk's slots, instead of the kernel-argument block through the scalar cache
+  __shared__ uint64_t s_ob[kBufOut ? 4 : 1];
   // in-loop statistics (INL): the chunk's pushed tasks, one slot per lane (publish c0 + lane): arrival at
   // the node, completion, service << 8 | status (0: not pushed); accumulated once per chunk
   __shared__ int64_t s_qa[INL ? kWave : 1];
@@ -791,6 +807,14 @@ __device__ __forceinline__ void replay_body(const ReplayArgs& A, const int r, co
     }
   }
   if constexpr (kBufOut) s_os[lane] = 0u;
+  if constexpr (kBufOut) {
+    if (lane == 0) {
+      s_ob[0] = (uint64_t)(uintptr_t)(A.out_node + tbase);
+      s_ob[1] = (uint64_t)(uintptr_t)(A.out_status + tbase);
+      s_ob[2] = (uint64_t)(uintptr_t)(A.out_start + tbase);
+      s_ob[3] = (uint64_t)(uintptr_t)(A.out_done + tbase);
+    }
+  }
   __syncthreads();
   int64_t gen_carry = 0;
   if constexpr (GEN) gen_carry = (int64_t)~wave_min_u64(~ul_max) + 1;
@@ -1177,20 +1201,24 @@ __device__ __forceinline__ void replay_body(const ReplayArgs& A, const int r, co
     }
     if constexpr (kBufOut) {
       // the chunk's outputs (also after an error ended it: the tasks pushed so far)
+      // (global address space stated: a pointer rebuilt from an integer is a flat one otherwise)
+      using G32 = __attribute__((address_space(1))) int32_t*;
+      using G8 = __attribute__((address_space(1))) uint8_t*;
+      using G64 = __attribute__((address_space(1))) int64_t*;
       const uint32_t so = s_os[lane];
       if (ballot(so != 0u)) {
         if (so != 0u) {
-          const size_t o = tbase + (size_t)c0;
-          const uint32_t l = lane_now();
           const int64_t dn = s_od[lane];
-          // nontemporal: the outputs are re-read only by the epilogue, long
-          // after they left L2; the ring's head lines keep the cache
           const uint32_t sS = s_oS[lane];
           const uint32_t nd = kPack ? pack_task(s_on[lane], sS, so) : (uint32_t)s_on[lane];
-          __builtin_nontemporal_store((int32_t)nd, (A.out_node + o) + l);
-          __builtin_nontemporal_store((uint8_t)so, (A.out_status + o) + l);
-          __builtin_nontemporal_store(dn - ticks_of(sS), (A.out_start + o) + l);
-          __builtin_nontemporal_store(dn, (A.out_done + o) + l);
+          const uint64_t b_node = s_ob[0], b_status = s_ob[1], b_start = s_ob[2], b_done = s_ob[3];
+          const uint32_t ol = (uint32_t)c0 + lane_now();  // (c0 + lane < T < 2^31)
+          // nontemporal: the outputs are re-read only by the epilogue, long
+          // after they left L2; the ring's head lines keep the cache
+          __builtin_nontemporal_store((int32_t)nd, (G32)b_node + ol);
+          __builtin_nontemporal_store((uint8_t)so, (G8)b_status + ol);
+          __builtin_nontemporal_store(dn - ticks_of(sS), (G64)b_start + ol);
+          __builtin_nontemporal_store(dn, (G64)b_done + ol);
           s_os[lane] = 0u;
         }
         ops += 4u;

@@ -154,6 +154,24 @@ __device__ __forceinline__ bool qtime_raw(int64_t now, int64_t a, int64_t& raw) 
   return simtime_to_int64(mul_rn((double)(now - qs), 1000.0), raw);
 }
 
+// toInt64 of a value the caller knows to be in range (|floor(x + 0.5)| < 2^63):
+// simtime_to_int64 without its range test and the select on it.
+__device__ __forceinline__ int64_t simtime_to_int64_inrange(double x) { return (int64_t)floor(add_rn(x, 0.5)); }
+
+// qtime_raw for the packed statistics pass.  a <= kMaxTick = 2^61 (the replay
+// checks it before the task is pushed: replay.hip `lerr`), so a * 1e-12 * 1e12
+// rounds to at most 2^61 (1 + 2^-51) < 2^63 and queueStartTime needs no range
+// test.  f: floor(x + 0.5) of the emission itself, an integral double; where the
+// result is true, (double)raw == f exactly, so f serves hist_bin_raw without
+// converting raw back.
+__device__ __forceinline__ bool qtime_raw_f(int64_t now, int64_t a, int64_t& raw, double& f) {
+  const int64_t qs = simtime_to_int64_inrange(mul_rn(1e12, simtime_dbl(a)));
+  f = floor(add_rn(mul_rn((double)(now - qs), 1000.0), 0.5));
+  const bool ok = fabs(f) < 0x1p63;
+  raw = ok ? (int64_t)f : 0;
+  return ok;
+}
+
 // (simTime() - t0) * 1000 with t0 a simtime_t (mqttApp2.cc:260,272,282)
 __device__ __forceinline__ bool ms_raw(int64_t d, int64_t& raw) {
   return simtime_to_int64(mul_rn((double)d, 1000.0), raw);
@@ -161,13 +179,15 @@ __device__ __forceinline__ bool ms_raw(int64_t d, int64_t& raw) {
 
 // histogram bin of a raw ms signal: whole part of the recorded double (ms)
 // (the bit length of (uint64)v for v >= 1 is v's binary exponent + 1, frexp's e)
-__device__ __forceinline__ int hist_bin_raw(int64_t raw) {
-  const double v = simtime_dbl(raw);
+// f: the raw value as a double, (double)raw
+__device__ __forceinline__ int hist_bin_raw(double f) {
+  const double v = mul_rn(f, 1e-12);
   if (!(v >= 1.0)) return 0;
   int b;
   (void)frexp(v, &b);
   return b > FOGNET_HIST_BINS - 1 ? FOGNET_HIST_BINS - 1 : b;
 }
+__device__ __forceinline__ int hist_bin_raw(int64_t raw) { return hist_bin_raw((double)raw); }
 
 // ---------------------------------------------------------------- statistics
 // Exact per-replication statistics: queueTime (ComputeBrokerApp3.cc:238) over
@@ -555,27 +575,46 @@ __device__ __forceinline__ void packed_load(PackedRows<UNROLL>& s, const int64_t
 // l + 64, ...).  The loop is software-pipelined over two register sets: the
 // loads of the next UNROLL x 64 rows are issued before the current rows are
 // used, so the only waits in the loop are counted ones for the older set.
-// write_back (wave-uniform): store the clean node; off for the internal
-// scratch outputs of a statistics-only replay, which nobody reads afterwards.
 // kPerTask, s_busy, s_hist, dl_of, ab_tick/ab_task (one slot per lane): as
 // stats_accumulate.
-template <int UNROLL, bool kPerTask, class DlOf>
+// The wave-uniform flags are fixed per instantiation, so a row holds no branch on
+// them: kHist (the histograms are wanted) and kWriteBack (store the clean node;
+// off for the internal scratch outputs of a statistics-only replay, which nobody
+// reads afterwards).  kStatic = false takes both from the arguments at run time
+// instead (the rare per-task pass after an error or past 2^32 service seconds,
+// which also carries the energy flag: one instantiation instead of eight).
+// dl_of is read for two rows at a time, before the first one's arithmetic and
+// whatever their statuses are (every row's node index is in range: rows past the
+// end reload a pushed task): one LDS wait per pair instead of one inside every
+// queued row.  (All four rows of a block at once spill in replay_kernel<4, ...>.)
+// Counters: a lane sees n_lane = ceil((n - lane) / 64) < 2^25 tasks (n < 2^31), so
+// its queued tasks (status 4) and its overflowing emissions are counted in 32 bits,
+// and n_started = n_lane - queued, n_qtime = queued - overflowing follow after the
+// loop (a pushed task's status is 4 or 5).
+template <int UNROLL, bool kPerTask, bool kStatic, bool kHist, bool kWriteBack, class DlOf>
 __device__ __forceinline__ void stats_accumulate_packed(const ReplayArgs& A, size_t tbase, int n_tasks, int lane_id,
-                                                        bool write_back, Acc& a, unsigned long long* s_busy,
+                                                        bool write_back_rt, Acc& a, unsigned long long* s_busy,
                                                         uint32_t* s_hist, DlOf dl_of, int64_t* ab_tick,
                                                         int32_t* ab_task) {
   if (n_tasks <= 0) return;
   const uint32_t n = (uint32_t)n_tasks, lane = (uint32_t)lane_id & (uint32_t)(kWave - 1);
   const bool energy = kPerTask && A.p_busy != nullptr;
-  const bool hist = A.hist != nullptr;
+  const bool hist = kStatic ? kHist : A.hist != nullptr;
+  const bool write_back = kStatic ? kWriteBack : write_back_rt;
   const int64_t* const arrive = A.arrive + tbase;
   const int64_t* const done = A.out_done + tbase;
   int32_t* const word = A.out_node + tbase;
   SqParts rsq = {}, qsq = {};  // squares of the response and of |queueTime|: folded into `a` after the loop
+  uint32_t n4 = 0u, nqo = 0u;
   auto rows = [&](const PackedRows<UNROLL>& s, uint32_t ib) {  // ib < n
     const uint32_t lim = n - 1u - ib;
+    int64_t dl[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
+      if (u % 2 == 0) {  // this row's and the next one's downlink: one LDS wait per pair of rows
+        dl[u] = dl_of((int)(s.w[u] & 0xFFu));
+        if (u + 1 < UNROLL) dl[u + 1] = dl_of((int)(s.w[u + 1] & 0xFFu));
+      }
       const uint32_t o = (uint32_t)(u * kWave) + lane;
       if (o <= lim) {
         const uint32_t k = s.w[u] & 0xFFu, S = (s.w[u] >> 8) & 0xFFu, status = s.w[u] >> 16;
@@ -593,21 +632,19 @@ __device__ __forceinline__ void stats_accumulate_packed(const ReplayArgs& A, siz
         a.rmax = max(a.rmax, resp);
         if (hist) atomicAdd(&s_hist[FOGNET_HIST_BINS + hist_bin(resp)], 1u);
         if (status == 4u) {  // queueTime emission (ComputeBrokerApp3.cc:238), enqueued at its arrival
-          a.n4 += 1u;
+          n4 += 1u;
           int64_t raw;
-          if (qtime_raw(start, s.t[u] + dl_of((int)k), raw)) {  // (acc_qtime, the squares apart)
+          double f;
+          if (qtime_raw_f(start, s.t[u] + dl[u], raw, f)) {  // (acc_qtime, the squares apart)
             add128(a.qs_lo, a.qs_hi, (uint64_t)raw, raw < 0 ? ~(uint64_t)0 : 0u);  // two's complement
             sq_parts_add(qsq, raw < 0 ? (uint64_t)0 - (uint64_t)raw : (uint64_t)raw);
             a.qmin = min(a.qmin, raw);
             a.qmax = max(a.qmax, raw);
-            a.nqt += 1u;
-            if (hist) atomicAdd(&s_hist[hist_bin_raw(raw)], 1u);
+            if (hist) atomicAdd(&s_hist[hist_bin_raw(f)], 1u);
           } else {  // the reference throws there: its abort point
-            a.nqo += 1u;
+            nqo += 1u;
             abort_min(ab_tick[lane], ab_task[lane], start, (int32_t)(ib + o));
           }
-        } else {
-          a.n5 += 1u;
         }
       }
     }
@@ -625,6 +662,12 @@ __device__ __forceinline__ void stats_accumulate_packed(const ReplayArgs& A, siz
     ib += kStep;
     if (ib >= n) break;
   }
+  const uint32_t n_lane = (n + (uint32_t)(kWave - 1) - lane) >> 6;  // tasks lane, lane + 64, ... < n
+  static_assert(kWave == 64, "n_lane shifts by log2 of the wave size");
+  a.n4 += n4;
+  a.n5 += n_lane - n4;
+  a.nqt += n4 - nqo;
+  a.nqo += nqo;
   uint64_t top = 0u;  // (the response's sum of squares is a 128-bit field: modulo 2^128, as add_moment)
   sq_parts_fold(rsq, a.rq_lo, a.rq_hi, top);
   sq_parts_fold(qsq, a.qq_lo, a.qq_hi, a.qq_top);
