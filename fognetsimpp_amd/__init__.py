@@ -14,6 +14,7 @@ from .engine import (NEVER, BatchResult, V2Result, BrokerBaseApp2, BrokerBaseApp
                      window_stats, reduce_window_stats, merge_window_stats, summarize_window,
                      quantiles, job_quantiles, summarize_quantiles,
                      queue_stats, reduce_queue_stats, merge_queue_stats,
+                     compare, reduce_compare, merge_compare,
                      run_assigned, assign_round_robin, assign_random)
 from . import formats  # noqa: E402,F401
 
@@ -24,4 +25,5 @@ __all__ = ["Context", "BrokerBaseApp2", "BrokerBaseApp3", "BatchResult", "V2Resu
            "window_stats", "reduce_window_stats", "merge_window_stats", "summarize_window",
            "quantiles", "job_quantiles", "summarize_quantiles",
            "queue_stats", "reduce_queue_stats", "merge_queue_stats",
+           "compare", "reduce_compare", "merge_compare",
            "run_assigned", "assign_round_robin", "assign_random"]

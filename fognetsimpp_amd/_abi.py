@@ -137,6 +137,24 @@ QUEUE_STATS_DTYPE = np.dtype([("n_enq", np.int64), ("max_len", np.int64), ("obse
 assert QUEUE_STATS_DTYPE.itemsize == C.sizeof(QueueStats) == 176
 
 
+COMPARE_COUNTS = ("n_done_both", "n_done_only_a", "n_done_only_b", "n_done_neither", "n_better", "n_equal", "n_worse",
+                  "rep_better", "rep_equal", "rep_worse")
+COMPARE_SIGNALS = ("d_start", "d_service", "d_resp")
+COMPARE_STATUS = (5, 4, 9)  # index of a task status in trans
+
+
+class CompareStats(C.Structure):
+    _fields_ = [("status_a", C.c_int32), ("status_b", C.c_int32), ("n_reps", C.c_int64), ("n_pairs", C.c_int64),
+                ("n_moved", C.c_int64), ("trans", (C.c_int64 * 3) * 3)] + [(n, C.c_int64) for n in COMPARE_COUNTS] + \
+               [(n, Moments) for n in COMPARE_SIGNALS]
+
+
+COMPARE_STATS_DTYPE = np.dtype([("status_a", np.int32), ("status_b", np.int32), ("n_reps", np.int64),
+                                ("n_pairs", np.int64), ("n_moved", np.int64), ("trans", np.int64, (3, 3))] +
+                               [(n, np.int64) for n in COMPARE_COUNTS] + [(n, MOMENTS_DTYPE) for n in COMPARE_SIGNALS])
+assert COMPARE_STATS_DTYPE.itemsize == C.sizeof(CompareStats) == 400
+
+
 WINDOW_HEAD = (("n_publish", C.c_int64), ("n_complete", C.c_int64), ("busy_lo", C.c_uint64), ("busy_hi", C.c_uint64),
                ("insys_lo", C.c_uint64), ("insys_hi", C.c_uint64))
 WINDOW_SIGNALS = ("queue", "delay", "latency", "latencyH1", "taskTime")
@@ -266,6 +284,10 @@ SIGNATURES = {
     "fognet_reduce_queue_stats_dev": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, P]),
     "fognet_queue_stats_init": (None, [C.POINTER(QueueStats)]),
     "fognet_queue_stats_merge": (None, [C.POINTER(QueueStats), C.POINTER(QueueStats)]),
+    "fognet_compare_dev": (C.c_int, [P, C.POINTER(BatchIn), C.POINTER(BatchOut), C.POINTER(BatchOut), P, P, P]),
+    "fognet_reduce_compare_dev": (C.c_int, [P, P, C.c_int32, P, P]),
+    "fognet_compare_stats_init": (None, [C.POINTER(CompareStats)]),
+    "fognet_compare_stats_merge": (None, [C.POINTER(CompareStats), C.POINTER(CompareStats)]),
     "fognet_window_stats_init": (None, [C.POINTER(WindowStats)]),
     "fognet_window_stats_merge": (None, [C.POINTER(WindowStats), C.POINTER(WindowStats)]),
     "fognet_user_stats_init": (None, [C.POINTER(UserStats)]),
@@ -291,6 +313,8 @@ SIGNATURES = {
     "fognet_write_sca": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(JobStats), P]),
     "fognet_write_sca_nodes": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int]),
     "fognet_write_sca_queue": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int32, P, C.c_int]),
+    "fognet_write_sca_compare": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(CompareStats), P,
+                                           C.c_int]),
     "fognet_write_sca_users": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int]),
     "fognet_write_vec": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P, P, P, P, P, P]),
     "fognet_write_vec_users": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P, P, P, P,

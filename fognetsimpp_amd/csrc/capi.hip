@@ -913,6 +913,35 @@ int fognet_reduce_node_stats_dev(fognet_ctx* c, const fognet_node_stats* node_st
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "node reduce launch");
 }
 
+// (of `in` only R and T are read: no prepare(), which checks the trace and the policy)
+int fognet_compare_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out_a,
+                       const fognet_batch_out* out_b, fognet_compare_stats* cmp, int64_t* hist, void* stream) {
+  if (!c) return FOGNET_ERR_ARG;
+  if (!in || !out_a || !out_b) return fail(c, FOGNET_ERR_ARG, "null batch");
+  if (in->R < 0 || in->T < 0) return fail(c, FOGNET_ERR_ARG, "negative R/T");
+  if (in->R == 0) return FOGNET_OK;
+  if (!out_a->stats || !out_b->stats) return fail(c, FOGNET_ERR_ARG, "null stats");
+  for (const fognet_batch_out* o : {out_a, out_b})
+    if (in->T > 0 && (!o->node || !o->status || !o->start_tick || !o->done_tick))
+      return fail(c, FOGNET_ERR_ARG, "the comparison needs the per-task outputs of both replays (a statistics-only out has none)");
+  if (!cmp) return fail(c, FOGNET_ERR_ARG, "null cmp");
+  const int rc = set_device(c);
+  if (rc) return rc;
+  const hipError_t e = fognet::launch_compare(fognet::CompareIn{in->R, in->T, out_a, out_b}, cmp, hist, (hipStream_t)stream);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "compare launch");
+}
+
+int fognet_reduce_compare_dev(fognet_ctx* c, const fognet_compare_stats* cmp, int32_t R, fognet_compare_stats* out,
+                              void* stream) {
+  if (!c) return FOGNET_ERR_ARG;
+  if (R < 0) return fail(c, FOGNET_ERR_ARG, "negative R");
+  if (!out || (R > 0 && !cmp)) return fail(c, FOGNET_ERR_ARG, "null pointer");
+  const int rc = set_device(c);
+  if (rc) return rc;
+  const hipError_t e = fognet::launch_reduce_compare(cmp, R, out, (hipStream_t)stream);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "compare reduce launch");
+}
+
 int fognet_per_user_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out,
                               const int32_t* user_of, int32_t U, int32_t link_stride, const int64_t* user_ul,
                               const int64_t* user_dl, fognet_user_stats* per_user, int64_t* n_unassigned, void* stream) {
@@ -1406,6 +1435,27 @@ void fognet_queue_stats_merge(fognet_queue_stats* a, const fognet_queue_stats* b
   add128(a->area_lo, a->area_hi, b->area_lo, b->area_hi);
   for (int q = 0; q < FOGNET_QUEUE_LEVELS_MAX; ++q)
     add128(a->time_ge[q][0], a->time_ge[q][1], b->time_ge[q][0], b->time_ge[q][1]);
+}
+
+void fognet_compare_stats_init(fognet_compare_stats* s) {
+  if (!s) return;
+  memset(s, 0, sizeof *s);  // (statuses FOGNET_OK)
+  moments_init_host(&s->d_start);
+  moments_init_host(&s->d_service);
+  moments_init_host(&s->d_resp);
+}
+
+void fognet_compare_stats_merge(fognet_compare_stats* a, const fognet_compare_stats* b) {
+  if (!a || !b) return;
+  // the 22 counts from n_reps to rep_worse (a's statuses stay)
+  static_assert(offsetof(fognet_compare_stats, d_start) - offsetof(fognet_compare_stats, n_reps) == 22 * sizeof(int64_t),
+                "the counts are contiguous");
+  int64_t* const aw = &a->n_reps;
+  const int64_t* const bw = &b->n_reps;
+  for (int w = 0; w < 22; ++w) aw[w] = (int64_t)((uint64_t)aw[w] + (uint64_t)bw[w]);
+  moments_merge_host(&a->d_start, &b->d_start);
+  moments_merge_host(&a->d_service, &b->d_service);
+  moments_merge_host(&a->d_resp, &b->d_resp);
 }
 
 int fognet_gen_trace_dev(fognet_ctx* c, const fognet_gen_params* p, int64_t r0, int32_t R, int32_t T, int32_t N,

@@ -346,6 +346,8 @@ struct Options {
   int32_t windows = 0;       // ... and their number (0: ceil(stop / DT))
   std::vector<int32_t> quantile_ppm;  // --quantiles P[,P...]: the ranks in ppm (empty: no quantiles)
   std::vector<int64_t> queue_levels;  // --queue-stats [L1,L2,...]: the queue lengths (empty: no queue statistics)
+  int compare = 0;            // --compare: 0 none; rule B is 1 round-robin, 2 random, 3 REF_V3, 4 EXT_LAT
+  uint64_t compare_seed = 0;  // --compare random:SEED
   double p_busy = -1.0, p_idle = -1.0;
 };
 
@@ -499,6 +501,9 @@ void usage() {
       "  --queue-stats [L,...]  with --sca (BrokerBaseApp3 runs): append to every fog node's block the longest queue,\n"
       "                       its enqueues, its time average and the share of the run with L or more tasks\n"
       "                       waiting, for up to 8 ascending lengths (default 1,2,4,8,16,32,64,128)\n"
+      "  --compare rr|random[:SEED]|REF_V3|EXT_LAT   with --sca (BrokerBaseApp3 runs): replay the same traces under this\n"
+      "                       second rule as well and append the paired comparison, B (this rule) minus A (the run as\n"
+      "                       given): tasks moved, status changes, start, service and response differences\n"
       "  --device D           HIP device (default 0)\n"
       "  --world W --rank K --comm-id FILE   one process per GPU: rank K replays its block of the\n"
       "                       --reps replications; the job statistics are exchanged over RCCL\n"
@@ -528,6 +533,17 @@ int32_t parse_percent(const std::string& v) {
   const int64_t ppm = whole * 10000 + frac;
   if (ppm > 1000000) die(what + "lies outside [0, 100]");
   return (int32_t)ppm;
+}
+
+// "rr" / "random[:SEED]" of --assign and --compare: 1 round-robin, 2 random (its seed in `seed`); 0: neither
+int parse_assign_rule(const std::string& v, const std::string& opt, uint64_t& seed) {
+  if (v == "rr") return 1;
+  if (v == "random") return 2;
+  if (v.rfind("random:", 0) != 0) return 0;
+  const long long sd = parse_int(v.substr(7), opt + " random:SEED");
+  if (sd < 0) die(opt + " random:SEED: SEED must be >= 0");
+  seed = (uint64_t)sd;
+  return 2;
 }
 
 Options parse_args(int argc, char** argv) {
@@ -566,15 +582,12 @@ Options parse_args(int argc, char** argv) {
       else die("--policy: REF_V3 or EXT_LAT");
       o.policy_set = true;
     } else if (a == "--assign") {
+      o.assign = parse_assign_rule(need(i), "--assign", o.assign_seed);
+      if (!o.assign) die("--assign: rr or random[:SEED]");
+    } else if (a == "--compare") {
       const std::string v = need(i);
-      if (v == "rr") o.assign = 1;
-      else if (v == "random") o.assign = 2;
-      else if (v.rfind("random:", 0) == 0) {
-        o.assign = 2;
-        const long long sd = parse_int(v.substr(7), "--assign random:SEED");
-        if (sd < 0) die("--assign random:SEED: SEED must be >= 0");
-        o.assign_seed = (uint64_t)sd;
-      } else die("--assign: rr or random[:SEED]");
+      o.compare = v == "REF_V3" ? 3 : v == "EXT_LAT" ? 4 : parse_assign_rule(v, "--compare", o.compare_seed);
+      if (!o.compare) die("--compare: rr, random[:SEED], REF_V3 or EXT_LAT");
     } else if (a == "--power") {
       const std::vector<std::string> p = split(need(i), ',');
       if (p.size() != 2) die("--power BUSY,IDLE");
@@ -655,6 +668,8 @@ Options parse_args(int argc, char** argv) {
   if (!o.queue_levels.empty() && o.sca.empty()) die("--queue-stats appends to the job's .sca: give --sca FILE");
   if (!o.queue_levels.empty() && o.world > 1)
     die("--queue-stats: the per-node records of several ranks are not combined (--world 1)");
+  if (o.compare && o.sca.empty()) die("--compare appends to the job's .sca: give --sca FILE");
+  if (o.compare && o.world > 1) die("--compare: the records of several ranks are not combined (--world 1)");
   if (o.assign && o.policy_set) die("--assign replaces the broker's decision: not together with --policy");
   if (o.world > 1 && o.comm_id.empty()) die("--world > 1 needs --comm-id FILE (the communicator id's rendezvous)");
   if (o.reps < o.world) die("--reps must be >= --world (every rank replays a block of replications)");
@@ -1054,6 +1069,61 @@ void add_run_attr(const std::string& path, const std::string& name, const std::s
   if (!w) die("cannot write " + path);
 }
 
+// the run's own rule (A of --compare) and the rule --compare names (B)
+std::string rule_name(const Options& o, const fognet_batch_in& in) {
+  return o.assign ? "assign:" + assign_name(o) : in.policy == FOGNET_POLICY_EXT_LAT ? "EXT_LAT" : "REF_V3";
+}
+
+Options compare_rule(const Options& o) {
+  Options b = o;
+  b.assign = o.compare <= 2 ? o.compare : 0;
+  b.assign_seed = o.compare_seed;
+  b.policy = o.compare == 4 ? FOGNET_POLICY_EXT_LAT : FOGNET_POLICY_REF_V3;
+  return b;
+}
+
+// --compare: the same traces replayed under rule B into a second set of outputs on the device, the paired
+// comparison with the run's own outputs (fognet_compare_dev), reduced over the replications
+// (fognet_reduce_compare_dev): one block appended to the job's .sca and one summary line.
+void append_compare(const Options& o, fognet_ctx* ctx, const DeviceBatch& db, const fognet_batch_in& in, int r0,
+                    const std::string& network, const std::string& run_id) {
+  const Options ob = compare_rule(o);
+  const size_t R = (size_t)in.R, RT = R * (size_t)in.T;
+  DeviceMem mem;
+  fognet_batch_in din = db.din;
+  din.policy = ob.policy;
+  fognet_batch_out b{};
+  b.node = mem.alloc<int32_t>(RT), b.status = mem.alloc<uint8_t>(RT), b.start_tick = mem.alloc<int64_t>(RT);
+  b.done_tick = mem.alloc<int64_t>(RT), b.stats = mem.alloc<fognet_rep_stats>(R);
+  const int32_t* d_assign = ob.assign ? mem.copy(make_assignment(ob, in, r0)) : nullptr;
+  fognet_compare_stats* d_cmp = mem.alloc<fognet_compare_stats>(R);
+  fognet_compare_stats* d_job = mem.alloc<fognet_compare_stats>(1);
+  std::vector<int64_t> hist(2 * FOGNET_HIST_BINS, 0);
+  int64_t* d_hist = mem.copy(hist);
+  mem.must();
+  if (ob.assign)
+    check_ctx(ctx, fognet_run_assigned_dev(ctx, &din, d_assign, &b, nullptr), "fognet_run_assigned_dev (--compare)");
+  else
+    check_ctx(ctx, fognet_run_batch_dev(ctx, &din, &b, nullptr), "fognet_run_batch_dev (--compare)");
+  const fognet_batch_out a = db.pass_out();
+  check_ctx(ctx, fognet_compare_dev(ctx, &din, &a, &b, d_cmp, d_hist, nullptr), "fognet_compare_dev");
+  check_ctx(ctx, fognet_reduce_compare_dev(ctx, d_cmp, in.R, d_job, nullptr), "fognet_reduce_compare_dev");
+  fognet_compare_stats job;
+  mem.sync();
+  mem.fetch(&job, d_job, 1), mem.fetch(hist.data(), d_hist, hist.size());
+  mem.must();
+  check(fognet_write_sca_compare(o.sca.c_str(), run_id.c_str(), network.c_str(), nullptr, &job, hist.data(), 1), "sca compare");
+  if (!o.quiet) {
+    // the mean of the exact signed 128-bit sum
+    const __int128 sum = (__int128)(((unsigned __int128)job.d_resp.sum_hi << 64) | job.d_resp.sum_lo);
+    const double mean_ms = job.d_resp.count ? (double)((long double)sum / (long double)job.d_resp.count / 1e9L) : 0.0;
+    std::printf("compare A=%s B=%s reps=%" PRId64 " pairs=%" PRId64 " moved=%" PRId64 " better=%" PRId64 " equal=%" PRId64
+                " worse=%" PRId64 " mean_response_diff_ms=%.9g\n",
+                rule_name(o, in).c_str(), rule_name(ob, din).c_str(), job.n_reps, job.n_pairs, job.n_moved, job.n_better,
+                job.n_equal, job.n_worse, mean_ms);
+  }
+}
+
 // BrokerBaseApp3 + ComputeBrokerApp3 (the batch engine; device entry points over one device copy of the batch).
 int run_v3(const Options& o, fognet_batch_in in, const std::string& network, const std::string& run_id,
            const UserSide* us = nullptr, int r0 = 0, int64_t stop = 0) {
@@ -1104,6 +1174,7 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
   if (!o.sca.empty() && o.assign) add_run_attr(o.sca, "assign", assign_name(o));
   if (!o.sca.empty() && o.node_stats) append_node_stats(o, ctx, *db, network, run_id);
   if (!o.sca.empty() && !o.queue_levels.empty()) append_queue_stats(o, ctx, *db, network, run_id, job.last_tick);
+  if (!o.sca.empty() && o.compare) append_compare(o, ctx, *db, in, r0, network, run_id);
   if (!o.sca.empty() && o.user_stats && us) append_user_stats(o, ctx, *db, *us, network, run_id);
   if (!o.sca.empty() && !o.quantile_ppm.empty() && us) append_quantiles(o, ctx, *db, *us, network, run_id);
   if (!o.vec.empty()) {  // replication 0's vectors (a failed replication has no complete outputs)
@@ -1121,7 +1192,7 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
   if (!o.quiet) {
     std::printf("policy=%s R=%d T=%d N=%d decisions=%" PRId64 " queued=%" PRId64 " started=%" PRId64
                 " failed_reps=%" PRId64 " makespan_ticks=%" PRId64 " max_pending=%" PRId64 "\n",
-                o.assign ? ("assign:" + assign_name(o)).c_str() : in.policy == FOGNET_POLICY_EXT_LAT ? "EXT_LAT" : "REF_V3", in.R, in.T, in.N, job.n_tasks, job.n_queued,
+                rule_name(o, in).c_str(), in.R, in.T, in.N, job.n_tasks, job.n_queued,
                 job.n_started, job.n_failed, job.last_tick, job.max_pending);
     std::vector<int64_t> per(in.N, 0);  // completed replications only (a failed one stops mid-trace)
     for (int32_t r = 0; r < in.R; ++r) {
@@ -1261,6 +1332,8 @@ int main(int argc, char** argv) {
   if (v2 && o.assign) die("--assign applies to BrokerBaseApp3 runs (the BrokerBaseApp2 broker serves tasks itself)");
   if (v2 && !o.queue_levels.empty())
     die("--queue-stats applies to BrokerBaseApp3 runs (the BrokerBaseApp2 nodes keep no requests vector)");
+  if (v2 && o.compare)
+    die("--compare applies to BrokerBaseApp3 runs (the BrokerBaseApp2 replay has other status codes and no closed pairing)");
   if (v2 && o.user_stats)
     die("--user-stats applies to BrokerBaseApp3 runs (the BrokerBaseApp2 model has no closed form for the user signals)");
   if (v2 && o.vec_users)

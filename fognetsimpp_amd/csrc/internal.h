@@ -493,6 +493,17 @@ hipError_t launch_queue_stats(const ReplayArgs& a, const QueueWs& w, const int64
                               int64_t t1, fognet_queue_stats* out, bool force_hbm, int stages, hipStream_t s);
 hipError_t launch_reduce_queue_stats(const fognet_queue_stats* in, const fognet_rep_stats* stats, int32_t R, int32_t N,
                                      fognet_queue_stats* out, hipStream_t s);
+// Paired comparison of two finished replays of the same traces and its job reduction
+// (compare_stats.hip): one workgroup per replication over the per-task outputs and records of a and
+// b (device pointers; all four per-task arrays and stats of each), no workspace.  hist
+// [2][FOGNET_HIST_BINS]: added to (nullable).  The reduction is one workgroup over any R; it goes
+// by the statuses the records carry.
+struct CompareIn {
+  int32_t R, T;
+  const fognet_batch_out *a, *b;
+};
+hipError_t launch_compare(const CompareIn& in, fognet_compare_stats* out, int64_t* hist, hipStream_t s);
+hipError_t launch_reduce_compare(const fognet_compare_stats* in, int32_t R, fognet_compare_stats* out, hipStream_t s);
 // v2 model replay (replay_v2.hip)
 size_t replay_v2_workspace_bytes(int32_t R, int32_t T, int32_t N, int32_t q_log2);
 hipError_t launch_replay_v2(const fognet_v2_in& in, const fognet_v2_out& out, void* workspace, int32_t q_log2,

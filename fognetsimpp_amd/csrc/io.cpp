@@ -581,6 +581,52 @@ int fognet_write_sca_users(const char* path, const char* run_id, const char* net
   return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_sca_users: write failed: ") + path);
 }
 
+int fognet_write_sca_compare(const char* path, const char* run_id, const char* network, const char* module,
+                             const fognet_compare_stats* job, const int64_t* hist, int append) {
+  if (!path || !run_id || !network || !job) return fail(FOGNET_ERR_ARG, "write_sca_compare: null argument");
+  FILE* f = fopen(path, append ? "a" : "w");
+  if (!f) return fail(FOGNET_ERR_ARG, std::string("write_sca_compare: cannot open ") + path);
+  if (!append) run_header(f, run_id, network);
+  const std::string mod = module ? std::string(module) : std::string(network) + ".compare";
+  const std::pair<const char*, int64_t> counts[] = {
+      {"replications", job->n_reps}, {"pairs", job->n_pairs},          {"moved", job->n_moved},
+      {"better", job->n_better},     {"equal", job->n_equal},          {"worse", job->n_worse},
+      {"doneOnlyA", job->n_done_only_a}, {"doneOnlyB", job->n_done_only_b}, {"repsBetter", job->rep_better},
+      {"repsEqual", job->rep_equal}, {"repsWorse", job->rep_worse}};
+  for (const auto& c : counts) fprintf(f, "scalar %s \tcompare:%s \t%lld\n", mod.c_str(), c.first, (long long)c.second);
+  static const int kStatus[3] = {5, 4, 9};  // trans' index order
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b)
+      fprintf(f, "scalar %s \tcompare:status%dto%d \t%lld\n", mod.c_str(), kStatus[a], kStatus[b], (long long)job->trans[a][b]);
+  const std::pair<const char*, const fognet_moments*> sigs[] = {
+      {"startDiff", &job->d_start}, {"serviceDiff", &job->d_service}, {"responseDiff", &job->d_resp}};
+  for (const auto& s : sigs) {  // tick values, signed: ms = ticks / 10^9
+    const fognet_moments& m = *s.second;
+    const uint64_t S[3] = {m.sum_lo, m.sum_hi, (int64_t)m.sum_hi < 0 ? ~(uint64_t)0 : 0};
+    const uint64_t Q[3] = {m.sq_lo, m.sq_hi, m.sq_top};
+    statistic(f, mod, s.first, "stats", moments(m.count, S, Q, m.min_raw, m.max_raw, true, false));
+    stat_attrs(f, s.first, "stats");
+  }
+  if (hist) {
+    static const char* const kSide[2] = {"responseDiff:earlier", "responseDiff:later"};
+    for (int side = 0; side < 2; ++side) {
+      Moments m;
+      m.count = 0;
+      for (int b = 0; b < FOGNET_HIST_BINS; ++b) m.count += hist[side * FOGNET_HIST_BINS + b];
+      m.mean = m.stddev = m.sum = m.sqrsum = m.min = m.max = NAN;  // (of one side alone: not recorded)
+      statistic(f, mod, kSide[side], "histogram", m);
+      stat_attrs(f, kSide[side], "histogram");
+      fprintf(f, "bin\t-INF\t0\n");
+      for (int b = 0; b < FOGNET_HIST_BINS; ++b) {
+        const double lo = b == 0 ? 0.0 : ldexp(1.0, b - 1);  // fognet_write_sca's bins
+        fprintf(f, "bin\t%s\t%lld\n", num(lo).c_str(), (long long)hist[side * FOGNET_HIST_BINS + b]);
+      }
+    }
+  }
+  const bool ok = ferror(f) == 0;
+  return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_sca_compare: write failed: ") + path);
+}
+
 // a rank in ppm as its exact percent: four decimals, trailing zeros trimmed
 static std::string percent_str(int32_t ppm) {
   char b[32];

@@ -1,5 +1,5 @@
 // signals.h — what the passes over a finished replay share (user_stats.hip, node_stats.hip,
-// per_user_stats.hip, signal_vectors.hip, window_stats.hip), each stated once: which replications and tasks a
+// per_user_stats.hip, signal_vectors.hip, window_stats.hip, compare_stats.hip), each stated once: which replications and tasks a
 // pass reads, the per-task row and the loop that streams it, the emission rule of a decided
 // publish, the moments of one signal with their wave merge and atomic commit, the empty
 // record, the frame of a pass keyed by node or user, and the job reduction of its records.
@@ -15,6 +15,8 @@
 // carry no state back into the decision loop, so every signal is a closed form of the replay
 // outputs; tests/oracle_lib restates them as real FES events.
 #pragma once
+#include <type_traits>
+
 #include "replay_common.h"
 
 namespace fognet {
@@ -61,22 +63,28 @@ __device__ __forceinline__ Row load_row(const ReplayArgs& A, const int32_t* user
 
 // A kPassThreads workgroup streams replication r's first n tasks, coalesced: 64 tasks per
 // wavefront and step, the next step's loads in flight while f(row, task, task < n) handles
-// this one.  Lanes past n reload the chunk's first task (in bounds, unused).
+// this one.  Lanes past n reload the chunk's first task (in bounds, unused).  The row is whatever
+// load(offset) returns (compare_stats.hip streams the rows of two replays as one); T: tasks per replication.
 template <class Load, class F>
-__device__ __forceinline__ void stream_rows(const ReplayArgs& A, int r, int n, Load&& load, F&& f) {
+__device__ __forceinline__ void stream_rows(int T, int r, int n, Load&& load, F&& f) {
+  using RowT = decltype(load((size_t)0));
   const int lane = (int)threadIdx.x & (kWave - 1), wave = (int)threadIdx.x / kWave;
-  const size_t tbase = (size_t)r * (size_t)A.T;
+  const size_t tbase = (size_t)r * (size_t)T;
   const int chunks = (n + kWave - 1) / kWave;
   auto offset_of = [&](int c) { return tbase + (size_t)(c * kWave + lane < n ? c * kWave + lane : c * kWave); };
-  Row cur{};
+  RowT cur{};
   if (wave < chunks) cur = load(offset_of(wave));
   for (int c = wave; c < chunks; c += kPassWaves) {
-    Row nxt = cur;
+    RowT nxt = cur;
     if (c + kPassWaves < chunks) nxt = load(offset_of(c + kPassWaves));
     const int i = c * kWave + lane;
     f(cur, i, i < n);
     cur = nxt;
   }
+}
+template <class Load, class F>
+__device__ __forceinline__ void stream_rows(const ReplayArgs& A, int r, int n, Load&& load, F&& f) {
+  stream_rows(A.T, r, n, load, f);
 }
 
 // ---------------------------------------------------------------- the emission rule
@@ -201,6 +209,19 @@ __device__ __forceinline__ void wave_merge2(Sig& a, Sig& b, Head& head) {
     sig_merge(b, ob);
   }
 }
+// its twin over three signals (compare_stats.hip)
+template <class Head>
+__device__ __forceinline__ void wave_merge3(Sig& a, Sig& b, Sig& c, Head& head) {
+#pragma unroll 1
+  for (int m = kWave / 2; m > 0; m >>= 1) {
+    const Head oh = head.shfl_xor(m);
+    const Sig oa = sig_shfl_xor(a, m), ob = sig_shfl_xor(b, m), oc = sig_shfl_xor(c, m);
+    head.merge(oh);
+    sig_merge(a, oa);
+    sig_merge(b, ob);
+    sig_merge(c, oc);
+  }
+}
 
 __device__ __forceinline__ void commit_sig(fognet_moments* m, uint64_t n, uint64_t ovf, const Sig& s) {
   atomic_add(&m->overflow, ovf);
@@ -287,8 +308,15 @@ __device__ __forceinline__ void keyed_end(typename Ops::Rec* row, int keys, cons
 }
 
 // Job reduction: workgroup j merges column j of the [R][K] records of the replications that
-// ran to their end; its threads stride over the replications, then a tree in LDS.
+// ran to their end; its threads stride over the replications, then a tree in LDS.  An Ops with
+// included(rec) names its own records instead (a record that carries the statuses it depends on:
+// no stats array is read).
 constexpr int kReduceThreads = 128;
+
+template <class Ops, class = void>
+struct ops_names_included : std::false_type {};
+template <class Ops>
+struct ops_names_included<Ops, std::void_t<decltype(&Ops::included)>> : std::true_type {};
 
 template <class Ops>
 __global__ __launch_bounds__(kReduceThreads) void record_reduce_kernel(const typename Ops::Rec* in,
@@ -298,8 +326,14 @@ __global__ __launch_bounds__(kReduceThreads) void record_reduce_kernel(const typ
   __shared__ Rec sh[kReduceThreads];
   const int j = blockIdx.x;
   Rec a = empty_record<Ops>();
-  for (int r = threadIdx.x; r < R; r += kReduceThreads)
-    if (stats[r].status == FOGNET_OK) Ops::merge(a, in[(size_t)r * (size_t)K + (size_t)j]);
+  for (int r = threadIdx.x; r < R; r += kReduceThreads) {
+    const Rec& x = in[(size_t)r * (size_t)K + (size_t)j];
+    if constexpr (ops_names_included<Ops>::value) {
+      if (Ops::included(x)) Ops::merge(a, x);
+    } else {
+      if (stats[r].status == FOGNET_OK) Ops::merge(a, x);
+    }
+  }
   sh[threadIdx.x] = a;
   __syncthreads();
   for (int w = kReduceThreads / 2; w > 0; w >>= 1) {

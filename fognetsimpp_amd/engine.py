@@ -101,6 +101,11 @@ def _batch_in(trace: dict, R, T, N, stride, policy, *, ring_capacity=0, power=Fa
         region=opt(region, "region"), hier_up_tick=hier_up_tick, hier_threshold_s=hier_threshold_s, flags=flags)
 
 
+def _batch_in_dims(R: int, T: int) -> _abi.BatchIn:
+    """fognet_batch_in of a pass that reads R and T alone (fognet_compare_dev): no trace, no policy."""
+    return _abi.BatchIn(R=R, T=T)
+
+
 def _batch_out(out, *, energy=False, hist=False, escalated=False) -> _abi.BatchOut:
     """fognet_batch_out of a BatchResult: the per-task arrays and the records, and what the flags add."""
     return _abi.BatchOut(
@@ -666,6 +671,65 @@ def merge_queue_stats(records) -> np.ndarray:
             b = _abi.QueueStats.from_buffer_copy(rec[j].tobytes())
             lib.fognet_queue_stats_merge(C.byref(acc[j]), C.byref(b))
     return np.frombuffer(bytes(acc), dtype=_abi.QUEUE_STATS_DTYPE).copy()
+
+
+def compare(ctx: Context, out_a: BatchResult, out_b: BatchResult, res: torch.Tensor | None = None,
+            hist: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """Paired comparison (fognet_compare_dev) of two finished replays of the same traces on the
+    current stream (or ``stream``): per replication the tasks that moved to another node, the
+    status transitions, which run completed what, and the exact moments of B minus A of the start,
+    the service and the completion of the tasks both completed (ticks).  ``out_a`` / ``out_b``:
+    the results of :func:`run_batch` under any policy or of :func:`run_assigned` on one trace;
+    no trace is read, and that both belong to the same traces is the caller's word.
+    Returns the device buffer of the records, uint8 [R * sizeof(fognet_compare_stats)]
+    (``.cpu().numpy().view(_abi.COMPARE_STATS_DTYPE)`` gives [R] records); ``res``: write into this
+    buffer instead of a new one.  ``hist``: int64 [2, 64] on the device, ADDED to: the pairs that
+    finished earlier (row 0) and later (row 1) under B by |difference|, whole ms in log2 bins, of
+    the replications that are OK in both runs.  A replication that failed in either run gets the
+    empty record with the two statuses."""
+    shaped = next((o.node for o in (out_a, out_b) if o.node is not None), None)
+    if shaped is None:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "compare needs the per-task outputs (a statistics-only result has none)")
+    R, T = shaped.shape
+    dev = shaped.device
+    for o in (out_a, out_b):
+        if o.stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize or (o.node is not None and tuple(o.node.shape) != (R, T)):
+            raise FognetError(_abi.FOGNET_ERR_ARG, "compare: the two results disagree on R/T")
+    if hist is not None and (hist.dtype != torch.int64 or hist.numel() != 2 * _abi.HIST_BINS or hist.device != dev
+                             or not hist.is_contiguous()):
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"hist: a contiguous int64 [2, {_abi.HIST_BINS}] tensor on {dev}")
+    nres = R * _abi.COMPARE_STATS_DTYPE.itemsize
+    res = _record_buffer(res, nres, dev, "res", alloc=max(nres, 1))
+    bi, ba, bb = _batch_in_dims(R, T), _batch_out(out_a), _batch_out(out_b)
+    ctx.check(ctx._lib.fognet_compare_dev(ctx.handle, C.byref(bi), C.byref(ba), C.byref(bb), _ptr(res), _ptr(hist),
+                                          _stream_ptr(dev, stream)), "compare")
+    return res[:nres]
+
+
+def reduce_compare(ctx: Context, cmp: torch.Tensor, R: int, out: torch.Tensor | None = None, stream=None) -> np.ndarray:
+    """Exact job reduction of comparison records on the device (fognet_reduce_compare_dev): the
+    merge of the records whose two statuses are OK.  ``cmp``: :func:`compare`'s buffer.  Returns
+    COMPARE_STATS_DTYPE [1]; ``out``: the device buffer written to."""
+    nout = _abi.COMPARE_STATS_DTYPE.itemsize
+    dev = cmp.device
+    out = _record_buffer(out, nout, dev, "out")
+    if cmp.numel() < R * nout:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "cmp smaller than R replications")
+    ctx.check(ctx._lib.fognet_reduce_compare_dev(ctx.handle, _ptr(cmp), R, _ptr(out), _stream_ptr(dev, stream)),
+              "reduce_compare")
+    return out[:nout].cpu().numpy().view(_abi.COMPARE_STATS_DTYPE)
+
+
+def merge_compare(records) -> np.ndarray:
+    """Exact host merge of comparison records (fognet_compare_stats_merge) into one, a
+    COMPARE_STATS_DTYPE scalar array: counts and moments add, extrema combine, statuses OK."""
+    lib = _abi.load()
+    acc = _abi.CompareStats()
+    lib.fognet_compare_stats_init(C.byref(acc))
+    for rec in np.ascontiguousarray(records, dtype=_abi.COMPARE_STATS_DTYPE).reshape(-1):
+        b = _abi.CompareStats.from_buffer_copy(rec.tobytes())
+        lib.fognet_compare_stats_merge(C.byref(acc), C.byref(b))
+    return np.frombuffer(bytes(acc), dtype=_abi.COMPARE_STATS_DTYPE).copy()[0]
 
 
 def per_user_stats(ctx: Context, trace: dict, out: BatchResult, user_of, user_ul, user_dl,

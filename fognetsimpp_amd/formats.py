@@ -126,6 +126,24 @@ def write_sca_queue(path: str, queue, levels, node_id=None, append: bool = False
                                               _p(lv), lv.size, _p(nid), 1 if append else 0), "write_sca_queue")
 
 
+def write_sca_compare(path: str, job, hist=None, module: str | None = None, append: bool = False,
+                      run_id: str = "General-0-fognet", network: str = "FogNet") -> None:
+    """`.sca` block of one COMPARE_STATS_DTYPE job record (fognet_write_sca_compare) under ``module``
+    (default <network>.compare): the compare:* scalars, startDiff / serviceDiff / responseDiff
+    statistics in ms and, with ``hist`` (int64 [2, 64]), the earlier / later histograms.
+    ``append``: add it to the file :func:`write_sca` wrote instead of starting a new one."""
+    rec = np.ascontiguousarray(job, dtype=_abi.COMPARE_STATS_DTYPE).reshape(-1)
+    if rec.size != 1:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "write_sca_compare: one job record")
+    h = np.ascontiguousarray(hist, dtype=np.int64).reshape(-1) if hist is not None else None
+    if h is not None and h.size != 2 * _abi.HIST_BINS:
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"write_sca_compare: hist is int64 [2, {_abi.HIST_BINS}]")
+    c = _abi.CompareStats.from_buffer_copy(rec.tobytes())
+    _check(_abi.load().fognet_write_sca_compare(path.encode(), run_id.encode(), network.encode(),
+                                                module.encode() if module is not None else None, C.byref(c), _p(h),
+                                                1 if append else 0), "write_sca_compare")
+
+
 def write_sca_users(path: str, users, user_module=None, append: bool = False, run_id: str = "General-0-fognet",
                     network: str = "FogNet") -> None:
     """Per-user `.sca` blocks of USER_STATS_DTYPE records [U] (fognet_write_sca_users):

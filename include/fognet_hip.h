@@ -956,6 +956,68 @@ int fognet_reduce_queue_stats_dev(fognet_ctx *ctx, const fognet_queue_stats *qs,
 void fognet_queue_stats_init(fognet_queue_stats *s);
 void fognet_queue_stats_merge(fognet_queue_stats *acc, const fognet_queue_stats *other);
 
+/* Paired comparison of two replays of the same traces, A and B (two policies, a policy against
+ * fognet_run_assigned_dev, ...): task i of replication r is the same publish in both, so every
+ * difference below is B minus A of one task, and the publish tick arrive_tick cancels in all of
+ * them.  That both outputs belong to the same traces is the caller's word.
+ * Pairs: replication r is COMPARED iff stats_a[r].status and stats_b[r].status are each FOGNET_OK
+ * or FOGNET_REF_ABORTED; its pairs are the task indices i < n_pairs = min(n_tasks of A, n_tasks of
+ * B), clamped to [0, T].  n_moved and trans count over all pairs.  A status byte outside {5, 4, 9}
+ * counts in no cell of trans; the node values are compared and never used as an index.
+ * Signals: over the pairs COMPLETED in both runs (done_tick >= 0 on both sides), in ticks,
+ *   d_start   = start_b - start_a
+ *   d_service = (done_b - start_b) - (done_a - start_a)
+ *   d_resp    = done_b - done_a            (per pair d_resp = d_start + d_service)
+ * each computed modulo 2^64 (outputs of a replay stay below 2^61 ticks, so nothing wraps); signed
+ * values with two's complement sums, like queue_sum; overflow is always 0.  A negative d_resp
+ * means the task finished earlier under B: "better".
+ * Replications: a compared replication has n_reps = 1 and exactly one of rep_better / rep_equal /
+ * rep_worse = 1, by the sign of its signed 128-bit d_resp sum (< 0: better; no completed pair:
+ * equal).  A replication that is not compared gets the EMPTY record -- counts 0, the three empty
+ * fognet_moments, n_reps = 0 -- which still carries the two statuses; none of its rows is read, on
+ * either side.
+ * Everything is an exact integer in any order of the updates, so two runs are byte-identical. */
+/* index of a task status in trans: 0 = started (5), 1 = queued (4), 2 = lost (9) */
+typedef struct fognet_compare_stats {
+    int32_t status_a, status_b;   /* stats[r].status of the two replications (a job record: FOGNET_OK) */
+    int64_t n_reps;               /* replications in the record */
+    int64_t n_pairs;              /* publishes decided in both: min(n_tasks_a, n_tasks_b), clamped to [0, T] */
+    int64_t n_moved;              /* pairs with node_a != node_b */
+    int64_t trans[3][3];          /* pairs by (status in A, status in B) */
+    int64_t n_done_both, n_done_only_a, n_done_only_b, n_done_neither;   /* done_tick >= 0 */
+    int64_t n_better, n_equal, n_worse;        /* of n_done_both: d_resp < 0, == 0, > 0 */
+    int64_t rep_better, rep_equal, rep_worse;  /* replications by the sign of their d_resp sum */
+    fognet_moments d_start, d_service, d_resp; /* over the n_done_both pairs, ticks, B minus A */
+} fognet_compare_stats;           /* 400 B, 8-B aligned */
+
+/* The comparison of two finished replays, on the device.  Of `in` only R and T are read: no trace
+ * column, link or policy field, so the pass serves every fognet_batch_out the library produces
+ * (REF_V3, EXT_LAT, EXT_HIER with or without out->escalated, fognet_run_assigned_dev, with or
+ * without down_tick).  out_a and out_b (device pointers): node, status, start_tick, done_tick and
+ * stats[r].{n_tasks,status} of each; out_a == out_b is allowed.  Writes cmp [R] (device), one
+ * record per replication.  hist (device, [2][FOGNET_HIST_BINS] int64, ADDED to, nullable): row 0
+ * takes the completed pairs with d_resp < 0, row 1 those with d_resp > 0, each binned by
+ * |d_resp| with the rule of histogram metric 1 (whole milliseconds, log2 bins); only replications
+ * with both statuses == FOGNET_OK add to it (the job rule), so its rows sum to the job record's
+ * n_better / n_worse.
+ * Refused, before anything is written (FOGNET_ERR_ARG): negative R or T, and with R > 0 a
+ * statistics-only out on either side (T > 0), NULL stats, NULL cmp.  R = 0 and T = 0 succeed.
+ * The call only enqueues on hip_stream and needs no workspace; nothing depends on what cmp held,
+ * and nothing outside cmp [R] and hist is written. */
+int fognet_compare_dev(fognet_ctx *ctx, const fognet_batch_in *in, const fognet_batch_out *out_a,
+                       const fognet_batch_out *out_b, fognet_compare_stats *cmp /* [R] */,
+                       int64_t *hist /* [2][FOGNET_HIST_BINS], ADDED to, nullable */, void *hip_stream);
+/* Job reduction (device pointers): *out = the exact merge of the records cmp[r] whose status_a and
+ * status_b are both FOGNET_OK (the record carries its statuses, so no stats array is passed); its
+ * own statuses are FOGNET_OK and n_reps is the number merged.  Any R; R = 0 gives the empty
+ * record.  Needs no workspace. */
+int fognet_reduce_compare_dev(fognet_ctx *ctx, const fognet_compare_stats *cmp, int32_t R,
+                              fognet_compare_stats *out, void *hip_stream);
+/* Host-side identity (the empty record, statuses FOGNET_OK) and exact merge: counts and moments
+ * add field by field, extrema combine; acc's statuses are left alone. */
+void fognet_compare_stats_init(fognet_compare_stats *s);
+void fognet_compare_stats_merge(fognet_compare_stats *acc, const fognet_compare_stats *other);
+
 /* Exact reduction of R per-replication stats (device pointers) into one job
  * record (device pointer).  Replications with status != OK count in n_failed
  * and contribute nothing else.  R > 4096 reduces through partial records in

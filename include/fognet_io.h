@@ -111,6 +111,21 @@ int fognet_write_sca_queue(const char *path, const char *run_id, const char *net
                            const fognet_queue_stats *qs, const int64_t *level, int32_t Q,
                            const int32_t *node_id, int append);
 
+/* OMNeT++ .sca block of a paired comparison (host; the job record of fognet_reduce_compare_dev and
+ * fognet_compare_dev's hist, fognet_hip.h "Paired comparison").  Under one module (nullable:
+ * <network>.compare) the scalars, as integers,
+ *   compare:replications, compare:pairs, compare:moved, compare:better, compare:equal,
+ *   compare:worse, compare:doneOnlyA, compare:doneOnlyB, compare:repsBetter, compare:repsEqual,
+ *   compare:repsWorse and the nine compare:status<a>to<b> with a, b in 5, 4, 9 (trans, row-major),
+ * then startDiff:stats, serviceDiff:stats and responseDiff:stats in ms (ticks / 10^9) with
+ * fognet_write_sca's fields and formatting, from the exact sums (count 0: -nan).  hist
+ * ([2][FOGNET_HIST_BINS], nullable): responseDiff:earlier:histogram (d_resp < 0) and
+ * responseDiff:later:histogram (d_resp > 0) over |d_resp| in fognet_write_sca's bin format;
+ * `field count` is the row's total, and the moments of one side alone are not recorded (-nan).
+ * append: as fognet_write_sca_nodes. */
+int fognet_write_sca_compare(const char *path, const char *run_id, const char *network, const char *module,
+                             const fognet_compare_stats *job, const int64_t *hist, int append);
+
 /* OMNeT++ .sca blocks of per-user records (host; fognet_per_user_stats_dev /
  * fognet_reduce_user_stats_dev, fognet_hip.h): per module
  * <network>.<user_module[u] or "user[u]">.udpApp[0] the statistics `latency:stats`,
