@@ -15,6 +15,7 @@ from .engine import (NEVER, BatchResult, V2Result, BrokerBaseApp2, BrokerBaseApp
                      quantiles, job_quantiles, summarize_quantiles,
                      queue_stats, reduce_queue_stats, merge_queue_stats,
                      compare, reduce_compare, merge_compare,
+                     reduce_groups, rep_metrics, group_from_reps, merge_group_stats, group_job, summarize_group,
                      run_assigned, assign_round_robin, assign_random)
 from . import formats  # noqa: E402,F401
 
@@ -26,4 +27,5 @@ __all__ = ["Context", "BrokerBaseApp2", "BrokerBaseApp3", "BatchResult", "V2Resu
            "quantiles", "job_quantiles", "summarize_quantiles",
            "queue_stats", "reduce_queue_stats", "merge_queue_stats",
            "compare", "reduce_compare", "merge_compare",
+           "reduce_groups", "rep_metrics", "group_from_reps", "merge_group_stats", "group_job", "summarize_group",
            "run_assigned", "assign_round_robin", "assign_random"]

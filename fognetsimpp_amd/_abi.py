@@ -155,6 +155,23 @@ COMPARE_STATS_DTYPE = np.dtype([("status_a", np.int32), ("status_b", np.int32), 
 assert COMPARE_STATS_DTYPE.itemsize == C.sizeof(CompareStats) == 400
 
 
+REP_METRICS = ("RESP_MEAN", "RESP_MAX", "QUEUE_MEAN", "QUEUE_MAX", "QUEUED_PPM", "MAKESPAN", "BUSY_S", "MAX_PENDING",
+               "ENERGY_UJ")  # FOGNET_METRIC_*: index = position
+GROUP_COUNTS = ("n_reps", "n_failed", "n_ref_aborted", "n_tasks", "n_queued", "n_started", "events")
+GROUP_LDS_MAX = 64  # FOGNET_GROUP_LDS_MAX
+
+
+class GroupStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in GROUP_COUNTS] + [("queue", Moments), ("resp", Moments),
+                                                         ("across", Moments * len(REP_METRICS))]
+
+
+GROUP_STATS_DTYPE = np.dtype([(n, np.int64) for n in GROUP_COUNTS] +
+                             [("queue", MOMENTS_DTYPE), ("resp", MOMENTS_DTYPE),
+                              ("across", MOMENTS_DTYPE, (len(REP_METRICS),))])
+assert GROUP_STATS_DTYPE.itemsize == C.sizeof(GroupStats) == 848
+
+
 WINDOW_HEAD = (("n_publish", C.c_int64), ("n_complete", C.c_int64), ("busy_lo", C.c_uint64), ("busy_hi", C.c_uint64),
                ("insys_lo", C.c_uint64), ("insys_hi", C.c_uint64))
 WINDOW_SIGNALS = ("queue", "delay", "latency", "latencyH1", "taskTime")
@@ -288,6 +305,13 @@ SIGNATURES = {
     "fognet_reduce_compare_dev": (C.c_int, [P, P, C.c_int32, P, P]),
     "fognet_compare_stats_init": (None, [C.POINTER(CompareStats)]),
     "fognet_compare_stats_merge": (None, [C.POINTER(CompareStats), C.POINTER(CompareStats)]),
+    "fognet_reduce_groups_dev": (C.c_int, [P, P, C.c_int32, P, C.c_int32, P, P, P, P, P]),
+    "fognet_rep_metrics": (None, [C.POINTER(RepStats), C.POINTER(C.c_int64), C.POINTER(C.c_uint32),
+                                  C.POINTER(C.c_uint32)]),
+    "fognet_group_stats_init": (None, [C.POINTER(GroupStats)]),
+    "fognet_group_stats_add_rep": (None, [C.POINTER(GroupStats), C.POINTER(RepStats)]),
+    "fognet_group_stats_merge": (None, [C.POINTER(GroupStats), C.POINTER(GroupStats)]),
+    "fognet_group_stats_job": (None, [C.POINTER(GroupStats), C.POINTER(JobStats)]),
     "fognet_window_stats_init": (None, [C.POINTER(WindowStats)]),
     "fognet_window_stats_merge": (None, [C.POINTER(WindowStats), C.POINTER(WindowStats)]),
     "fognet_user_stats_init": (None, [C.POINTER(UserStats)]),
@@ -315,6 +339,7 @@ SIGNATURES = {
     "fognet_write_sca_queue": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int32, P, C.c_int]),
     "fognet_write_sca_compare": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(CompareStats), P,
                                            C.c_int]),
+    "fognet_write_sca_groups": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int]),
     "fognet_write_sca_users": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, P, P, C.c_int]),
     "fognet_write_vec": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P, P, P, P, P, P]),
     "fognet_write_vec_users": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P, P, P, P,

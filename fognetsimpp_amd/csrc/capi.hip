@@ -942,6 +942,22 @@ int fognet_reduce_compare_dev(fognet_ctx* c, const fognet_compare_stats* cmp, in
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "compare reduce launch");
 }
 
+int fognet_reduce_groups_dev(fognet_ctx* c, const fognet_rep_stats* stats, int32_t R, const int32_t* group_of, int32_t G,
+                             fognet_group_stats* out, int64_t* metrics, uint32_t* defined, int64_t* n_ungrouped,
+                             void* stream) {
+  if (!c) return FOGNET_ERR_ARG;
+  if (R < 0) return fail(c, FOGNET_ERR_ARG, "negative R");
+  if (G <= 0) return fail(c, FOGNET_ERR_ARG, "G must be positive");
+  if (!out || (R > 0 && !stats)) return fail(c, FOGNET_ERR_ARG, "null pointer");
+  const int rc = set_device(c);
+  if (rc) return rc;
+  // FOGNET_GROUP_STATS=hbm: the accumulators are the caller's records for every G (the layout above
+  // FOGNET_GROUP_LDS_MAX groups), so small tests run both layouts on the same records
+  const hipError_t e = fognet::launch_reduce_groups(stats, R, group_of, G, out, metrics, defined, n_ungrouped,
+                                                    env_is("FOGNET_GROUP_STATS", "hbm"), (hipStream_t)stream);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "group reduce launch");
+}
+
 int fognet_per_user_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out,
                               const int32_t* user_of, int32_t U, int32_t link_stride, const int64_t* user_ul,
                               const int64_t* user_dl, fognet_user_stats* per_user, int64_t* n_unassigned, void* stream) {

@@ -29,6 +29,7 @@
 #include <cctype>
 #include <cinttypes>
 #include <climits>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -348,6 +349,7 @@ struct Options {
   std::vector<int64_t> queue_levels;  // --queue-stats [L1,L2,...]: the queue lengths (empty: no queue statistics)
   int compare = 0;            // --compare: 0 none; rule B is 1 round-robin, 2 random, 3 REF_V3, 4 EXT_LAT
   uint64_t compare_seed = 0;  // --compare random:SEED
+  bool rep_spread = false;    // --rep-spread: the spread of the per-replication metrics across the replications
   double p_busy = -1.0, p_idle = -1.0;
 };
 
@@ -505,6 +507,10 @@ void usage() {
       "                       second rule as well and append the paired comparison, B (this rule) minus A (the run as\n"
       "                       given): tasks moved, status changes, start, service and response differences\n"
       "  --device D           HIP device (default 0)\n"
+      "  --rep-spread         with --sca (BrokerBaseApp3 runs): append the block <network>.replications: per metric of a\n"
+      "                       replication (mean and maximum response and queue time, queued share, makespan, busy\n"
+      "                       seconds, longest pending ring, energy) its count, mean and standard deviation ACROSS the\n"
+      "                       replications (the method of independent replications), and print one summary line\n"
       "  --world W --rank K --comm-id FILE   one process per GPU: rank K replays its block of the\n"
       "                       --reps replications; the job statistics are exchanged over RCCL\n"
       "                       (fognet_allreduce_stats) and rank 0 writes the results; FILE carries\n"
@@ -584,6 +590,8 @@ Options parse_args(int argc, char** argv) {
     } else if (a == "--assign") {
       o.assign = parse_assign_rule(need(i), "--assign", o.assign_seed);
       if (!o.assign) die("--assign: rr or random[:SEED]");
+    } else if (a == "--rep-spread") {
+      o.rep_spread = true;
     } else if (a == "--compare") {
       const std::string v = need(i);
       o.compare = v == "REF_V3" ? 3 : v == "EXT_LAT" ? 4 : parse_assign_rule(v, "--compare", o.compare_seed);
@@ -670,6 +678,8 @@ Options parse_args(int argc, char** argv) {
     die("--queue-stats: the per-node records of several ranks are not combined (--world 1)");
   if (o.compare && o.sca.empty()) die("--compare appends to the job's .sca: give --sca FILE");
   if (o.compare && o.world > 1) die("--compare: the records of several ranks are not combined (--world 1)");
+  if (o.rep_spread && o.sca.empty()) die("--rep-spread appends to the job's .sca: give --sca FILE");
+  if (o.rep_spread && o.world > 1) die("--rep-spread: the group records of several ranks are not combined (--world 1)");
   if (o.assign && o.policy_set) die("--assign replaces the broker's decision: not together with --policy");
   if (o.world > 1 && o.comm_id.empty()) die("--world > 1 needs --comm-id FILE (the communicator id's rendezvous)");
   if (o.reps < o.world) die("--reps must be >= --world (every rank replays a block of replications)");
@@ -1124,6 +1134,35 @@ void append_compare(const Options& o, fognet_ctx* ctx, const DeviceBatch& db, co
   }
 }
 
+// --rep-spread: the job's replications as one group (fognet_reduce_groups_dev, G = 1): the mean and the
+// standard deviation of every per-replication metric across the replications, one block appended to the
+// job's .sca and one summary line.
+void append_rep_spread(const Options& o, fognet_ctx* ctx, const DeviceBatch& db, const fognet_batch_in& in,
+                       const std::string& network, const std::string& run_id) {
+  DeviceMem mem;
+  fognet_group_stats* d_group = mem.alloc<fognet_group_stats>(1);
+  mem.must();
+  check_ctx(ctx, fognet_reduce_groups_dev(ctx, db.dout.stats, in.R, nullptr, 1, d_group, nullptr, nullptr, nullptr, nullptr),
+            "fognet_reduce_groups_dev");
+  fognet_group_stats g;
+  mem.sync();
+  mem.fetch(&g, d_group, 1);
+  mem.must();
+  check(fognet_write_sca_groups(o.sca.c_str(), run_id.c_str(), network.c_str(), 1, &g, nullptr, 1), "sca groups");
+  if (!o.quiet) {
+    // mean and unbiased standard deviation of the per-replication mean response, from the exact sums
+    const fognet_moments& m = g.across[FOGNET_METRIC_RESP_MEAN];
+    const long double n = (long double)m.count;
+    const long double s = (long double)(__int128)(((unsigned __int128)m.sum_hi << 64) | m.sum_lo);
+    const long double q = ((long double)m.sq_top * 18446744073709551616.0L + (long double)m.sq_hi) * 18446744073709551616.0L +
+                          (long double)m.sq_lo;
+    const long double var = m.count > 1 ? (q - s * s / n) / (n - 1.0L) : 0.0L;
+    std::printf("rep-spread reps=%" PRId64 " failed=%" PRId64 " ok=%" PRId64 " resp_mean_ms=%.9g resp_mean_stddev_ms=%.9g\n",
+                g.n_reps, g.n_failed, m.count, m.count ? (double)(s / n / 1e9L) : 0.0,
+                (double)(sqrtl(var > 0.0L ? var : 0.0L) / 1e9L));
+  }
+}
+
 // BrokerBaseApp3 + ComputeBrokerApp3 (the batch engine; device entry points over one device copy of the batch).
 int run_v3(const Options& o, fognet_batch_in in, const std::string& network, const std::string& run_id,
            const UserSide* us = nullptr, int r0 = 0, int64_t stop = 0) {
@@ -1175,6 +1214,7 @@ int run_v3(const Options& o, fognet_batch_in in, const std::string& network, con
   if (!o.sca.empty() && o.node_stats) append_node_stats(o, ctx, *db, network, run_id);
   if (!o.sca.empty() && !o.queue_levels.empty()) append_queue_stats(o, ctx, *db, network, run_id, job.last_tick);
   if (!o.sca.empty() && o.compare) append_compare(o, ctx, *db, in, r0, network, run_id);
+  if (!o.sca.empty() && o.rep_spread) append_rep_spread(o, ctx, *db, in, network, run_id);
   if (!o.sca.empty() && o.user_stats && us) append_user_stats(o, ctx, *db, *us, network, run_id);
   if (!o.sca.empty() && !o.quantile_ppm.empty() && us) append_quantiles(o, ctx, *db, *us, network, run_id);
   if (!o.vec.empty()) {  // replication 0's vectors (a failed replication has no complete outputs)
@@ -1332,6 +1372,8 @@ int main(int argc, char** argv) {
   if (v2 && o.assign) die("--assign applies to BrokerBaseApp3 runs (the BrokerBaseApp2 broker serves tasks itself)");
   if (v2 && !o.queue_levels.empty())
     die("--queue-stats applies to BrokerBaseApp3 runs (the BrokerBaseApp2 nodes keep no requests vector)");
+  if (v2 && o.rep_spread)
+    die("--rep-spread applies to BrokerBaseApp3 runs (the BrokerBaseApp2 replay's fognet_v2_stats hold counts only)");
   if (v2 && o.compare)
     die("--compare applies to BrokerBaseApp3 runs (the BrokerBaseApp2 replay has other status codes and no closed pairing)");
   if (v2 && o.user_stats)

@@ -504,6 +504,13 @@ struct CompareIn {
 };
 hipError_t launch_compare(const CompareIn& in, fognet_compare_stats* out, int64_t* hist, hipStream_t s);
 hipError_t launch_reduce_compare(const fognet_compare_stats* in, int32_t R, fognet_compare_stats* out, hipStream_t s);
+// Replication groups (group_stats.hip): a clear kernel writes the G empty records and n_ungrouped,
+// then one lane per replication over stats [R] (device pointers; group_of, metrics, defined and
+// n_ungrouped nullable), no workspace.  Up to FOGNET_GROUP_LDS_MAX groups a workgroup accumulates in
+// LDS unless force_hbm.  R = 0: the clear kernel alone.
+hipError_t launch_reduce_groups(const fognet_rep_stats* stats, int32_t R, const int32_t* group_of, int32_t G,
+                                fognet_group_stats* out, int64_t* metrics, uint32_t* defined, int64_t* n_ungrouped,
+                                bool force_hbm, hipStream_t s);
 // v2 model replay (replay_v2.hip)
 size_t replay_v2_workspace_bytes(int32_t R, int32_t T, int32_t N, int32_t q_log2);
 hipError_t launch_replay_v2(const fognet_v2_in& in, const fognet_v2_out& out, void* workspace, int32_t q_log2,

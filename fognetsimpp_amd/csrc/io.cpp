@@ -627,6 +627,73 @@ int fognet_write_sca_compare(const char* path, const char* run_id, const char* n
   return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_sca_compare: write failed: ") + path);
 }
 
+// cStdDev's fields of integer values reported in units of 10^-e (their exact signed 128-bit sum
+// and 192-bit sum of squares, a fognet_moments): moments() with a free power of ten
+static Moments moments_pow10(const fognet_moments& x, int e) {
+  const long double div = powl(10.0L, e);
+  const uint64_t S[2] = {x.sum_lo, x.sum_hi}, Q[3] = {x.sq_lo, x.sq_hi, x.sq_top};
+  const bool neg = (int64_t)x.sum_hi < 0;
+  Big sa = big_of(S, 2);
+  if (neg) {  // |S| by two's complement negation
+    Big ext = sa;
+    for (int i = 2; i < 7; ++i) ext.l[i] = ~(uint64_t)0;
+    sa = big_sub(Big(), ext);
+  }
+  const long double s = (neg ? -1.0L : 1.0L) * big_ld(sa), q = big_ld(big_of(Q, 3));
+  Moments m;
+  m.count = x.count;
+  m.sum = (double)(s / div);
+  m.sqrsum = (double)(q / div / div);
+  m.mean = m.stddev = m.min = m.max = NAN;
+  if (x.count <= 0) return m;
+  const long double n = (long double)x.count;
+  m.mean = (double)(s / n / div);
+  m.min = (double)((long double)x.min_raw / div);
+  m.max = (double)((long double)x.max_raw / div);
+  if (x.count < 2) return m;  // cStdDev: variance undefined for a single value
+  const uint64_t nn[1] = {(uint64_t)x.count};
+  const Big nq = big_mul(big_of(nn, 1), big_of(Q, 3)), s2 = big_mul(sa, sa);
+  const long double num = big_ge(nq, s2) ? big_ld(big_sub(nq, s2)) : 0.0L;
+  m.stddev = (double)(sqrtl(num / (n * (n - 1.0L))) / div);
+  return m;
+}
+
+int fognet_write_sca_groups(const char* path, const char* run_id, const char* network, int32_t G,
+                            const fognet_group_stats* groups, const char* const* module, int append) {
+  if (!path || !run_id || !network || G < 0 || (G > 0 && !groups))
+    return fail(FOGNET_ERR_ARG, "write_sca_groups: bad argument");
+  if (module)
+    for (int32_t g = 0; g < G; ++g)
+      if (!module[g]) return fail(FOGNET_ERR_ARG, "write_sca_groups: null module name");
+  FILE* f = fopen(path, append ? "a" : "w");
+  if (!f) return fail(FOGNET_ERR_ARG, std::string("write_sca_groups: cannot open ") + path);
+  if (!append) run_header(f, run_id, network);
+  // FOGNET_METRIC_* order; the reported unit is 10^-e of the integer metric
+  static const struct {
+    const char* name;
+    int e;
+  } kMetric[FOGNET_REP_METRICS] = {{"respMean", 9},    {"respMax", 9},  {"queueMean", 12},  {"queueMax", 12}, {"queuedShare", 6},
+                                   {"makespan", 12},   {"busySeconds", 0}, {"maxPending", 0}, {"energy", 6}};
+  for (int32_t g = 0; g < G; ++g) {
+    const fognet_group_stats& s = groups[g];
+    const std::string mod = module   ? std::string(module[g])
+                            : G == 1 ? std::string(network) + ".replications"
+                                     : std::string(network) + ".group[" + std::to_string(g) + "]";
+    fprintf(f, "scalar %s \treplications \t%lld\n", mod.c_str(), (long long)s.n_reps);
+    fprintf(f, "scalar %s \t\"failed replications\" \t%lld\n", mod.c_str(), (long long)s.n_failed);
+    fprintf(f, "scalar %s \t\"replications the reference aborts\" \t%lld\n", mod.c_str(), (long long)s.n_ref_aborted);
+    for (int k = 0; k < FOGNET_REP_METRICS; ++k) {
+      statistic(f, mod, kMetric[k].name, "replications", moments_pow10(s.across[k], kMetric[k].e));
+      stat_attrs(f, kMetric[k].name, "replications");
+      if (s.across[k].overflow > 0)
+        fprintf(f, "scalar %s \t\"%s replications lost\" \t%lld\n", mod.c_str(), kMetric[k].name,
+                (long long)s.across[k].overflow);
+    }
+  }
+  const bool ok = ferror(f) == 0;
+  return (fclose(f) == 0 && ok) ? FOGNET_OK : fail(FOGNET_ERR_ARG, std::string("write_sca_groups: write failed: ") + path);
+}
+
 // a rank in ppm as its exact percent: four decimals, trailing zeros trimmed
 static std::string percent_str(int32_t ppm) {
   char b[32];

@@ -732,6 +732,109 @@ def merge_compare(records) -> np.ndarray:
     return np.frombuffer(bytes(acc), dtype=_abi.COMPARE_STATS_DTYPE).copy()[0]
 
 
+def reduce_groups(ctx: Context, stats: torch.Tensor, R: int, group_of=None, G: int = 1, metrics: bool = False,
+                  out: torch.Tensor | None = None, stream=None):
+    """Replication groups (fognet_reduce_groups_dev) on the current stream (or ``stream``): the job
+    reduction keyed by ``group_of`` (int32 [R], host or device; None: one group) and, per group,
+    the exact moments of the nine per-replication metrics (``_abi.REP_METRICS``) across its OK
+    replications.  ``stats``: the device buffer of [R] fognet_rep_stats of any replay
+    (``BatchResult.stats``).  Returns GROUP_STATS_DTYPE [G] and the number of replications whose
+    group lies outside [0, G); with ``metrics`` also int64 [R, 9] and uint32 [R] (the values and
+    which of them the moments took; every other entry is INT64_MIN).  ``out``: the device buffer
+    the records are written to (uint8, G * 848)."""
+    dev = stats.device
+    if R < 0 or stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
+        raise FognetError(_abi.FOGNET_ERR_ARG, "stats smaller than R replications")
+    gof = None
+    if group_of is not None:
+        gof = _to_dev(group_of, torch.int32, dev).reshape(-1)
+        if gof.numel() != R:
+            raise FognetError(_abi.FOGNET_ERR_ARG, "group_of: int32 [R]")
+    nout = max(G, 0) * _abi.GROUP_STATS_DTYPE.itemsize
+    out = _record_buffer(out, nout, dev, "out", alloc=max(nout, 1))
+    met = torch.empty((R, len(_abi.REP_METRICS)), dtype=torch.int64, device=dev) if metrics else None
+    dfn = torch.empty(max(R, 1), dtype=torch.int32, device=dev) if metrics else None
+    ung = torch.empty(1, dtype=torch.int64, device=dev)
+    ctx.check(ctx._lib.fognet_reduce_groups_dev(ctx.handle, _ptr(stats), R, _ptr(gof), G, _ptr(out), _ptr(met),
+                                                _ptr(dfn), _ptr(ung), _stream_ptr(dev, stream)), "reduce_groups")
+    rec = out[:nout].cpu().numpy().view(_abi.GROUP_STATS_DTYPE)
+    if not metrics:
+        return rec, int(ung.item())
+    return rec, int(ung.item()), met.cpu().numpy(), dfn[:R].cpu().numpy().view(np.uint32)
+
+
+def rep_metrics(rep):
+    """The nine metrics of one REP_STATS_DTYPE record (fognet_rep_metrics, host): int64 [9] values
+    (INT64_MIN where undefined or overflowed), the bits of the defined ones, the bits of those that
+    do not fit int64.  The record's status is not looked at."""
+    b = _abi.RepStats.from_buffer_copy(np.ascontiguousarray(rep).tobytes())
+    val = (C.c_int64 * len(_abi.REP_METRICS))()
+    dfn, ovf = C.c_uint32(), C.c_uint32()
+    _abi.load().fognet_rep_metrics(C.byref(b), val, C.byref(dfn), C.byref(ovf))
+    return np.array(val[:], dtype=np.int64), dfn.value, ovf.value
+
+
+def group_from_reps(reps) -> np.ndarray:
+    """Exact host reduction of REP_STATS_DTYPE records into one group record
+    (fognet_group_stats_add_rep, the host twin of fognet_reduce_groups_dev)."""
+    lib = _abi.load()
+    acc = _abi.GroupStats()
+    lib.fognet_group_stats_init(C.byref(acc))
+    for rec in np.atleast_1d(reps):
+        b = _abi.RepStats.from_buffer_copy(np.ascontiguousarray(rec).tobytes())
+        lib.fognet_group_stats_add_rep(C.byref(acc), C.byref(b))
+    return np.frombuffer(bytes(acc), dtype=_abi.GROUP_STATS_DTYPE).copy()[0]
+
+
+def merge_group_stats(records) -> np.ndarray:
+    """Exact host merge of group records (fognet_group_stats_merge) into one: ranks, shards, or
+    groups folded together."""
+    lib = _abi.load()
+    acc = _abi.GroupStats()
+    lib.fognet_group_stats_init(C.byref(acc))
+    for rec in np.ascontiguousarray(records, dtype=_abi.GROUP_STATS_DTYPE).reshape(-1):
+        b = _abi.GroupStats.from_buffer_copy(rec.tobytes())
+        lib.fognet_group_stats_merge(C.byref(acc), C.byref(b))
+    return np.frombuffer(bytes(acc), dtype=_abi.GROUP_STATS_DTYPE).copy()[0]
+
+
+def group_job(group) -> np.ndarray:
+    """One group record as a job record (fognet_group_stats_job): the integer fields of
+    :func:`reduce_stats` over the group's members, energy_j from the exact sum of microjoules."""
+    g = _abi.GroupStats.from_buffer_copy(np.ascontiguousarray(group, dtype=_abi.GROUP_STATS_DTYPE).tobytes())
+    job = _abi.JobStats()
+    _abi.load().fognet_group_stats_job(C.byref(g), C.byref(job))
+    return np.frombuffer(bytes(job), dtype=_abi.JOB_STATS_DTYPE).copy()[0]
+
+
+# reported unit of each metric as a power of ten (fognet_write_sca_groups): ms, ms, ms, ms, a fraction, s, s, tasks, J
+GROUP_METRIC_KEYS = ("respMean_ms", "respMax_ms", "queueMean_ms", "queueMax_ms", "queuedShare", "makespan_s", "busy_s",
+                     "maxPending", "energy_j")
+_GROUP_METRIC_EXP = (9, 9, 12, 12, 6, 12, 0, 0, 6)
+
+
+def summarize_group(group) -> dict:
+    """:func:`summarize` of the group's job record plus, under ``"replications_by_metric"``, per metric the
+    count, mean, stddev (unbiased, over replications), min and max in the units of the `.sca`
+    writer, and the replications lost to the int64 range."""
+    d = summarize(group_job(group))
+    across = {}
+    for k, (name, e) in enumerate(zip(GROUP_METRIC_KEYS, _GROUP_METRIC_EXP)):
+        m = group["across"][k]
+        n = int(m["count"])
+        s = _signed(int(m["sum_lo"]) | (int(m["sum_hi"]) << 64), 128)
+        q = int(m["sq_lo"]) | (int(m["sq_hi"]) << 64) | (int(m["sq_top"]) << 128)
+        unit = 10.0 ** -e
+        f = dict(count=n, overflow=int(m["overflow"]))
+        if n:
+            var = (n * q - s * s) / (n * (n - 1)) if n > 1 else 0
+            f.update(mean=s / n * unit, stddev=max(var, 0) ** 0.5 * unit if n > 1 else float("nan"),
+                     min=int(m["min_raw"]) * unit, max=int(m["max_raw"]) * unit)
+        across[name] = f
+    d["replications_by_metric"] = across
+    return d
+
+
 def per_user_stats(ctx: Context, trace: dict, out: BatchResult, user_of, user_ul, user_dl,
                    policy: str | int | None = None, res: torch.Tensor | None = None,
                    hier_up_tick: int | None = None, allow_unassigned: bool = False,

@@ -144,6 +144,24 @@ def write_sca_compare(path: str, job, hist=None, module: str | None = None, appe
                                                 1 if append else 0), "write_sca_compare")
 
 
+def write_sca_groups(path: str, groups, module=None, append: bool = False, run_id: str = "General-0-fognet",
+                     network: str = "FogNet") -> None:
+    """`.sca` blocks of GROUP_STATS_DTYPE records [G] (fognet_write_sca_groups): per group the
+    replication counts and one `<metric>:replications` statistic per metric across its
+    replications, under ``module[g]`` (default <network>.replications for one record, else
+    <network>.group[g]).  ``append``: add them to the file :func:`write_sca` wrote."""
+    rec = np.ascontiguousarray(groups, dtype=_abi.GROUP_STATS_DTYPE).reshape(-1)
+    names = None
+    if module is not None:
+        mods = [str(m).encode() for m in module]
+        if len(mods) != rec.size:
+            raise FognetError(_abi.FOGNET_ERR_ARG, "write_sca_groups: module length differs from the records'")
+        names = (C.c_char_p * len(mods))(*mods)
+    _check(_abi.load().fognet_write_sca_groups(path.encode(), run_id.encode(), network.encode(), rec.size, _p(rec),
+                                               C.cast(names, C.c_void_p) if names is not None else None,
+                                               1 if append else 0), "write_sca_groups")
+
+
 def write_sca_users(path: str, users, user_module=None, append: bool = False, run_id: str = "General-0-fognet",
                     network: str = "FogNet") -> None:
     """Per-user `.sca` blocks of USER_STATS_DTYPE records [U] (fognet_write_sca_users):

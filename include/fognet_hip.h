@@ -357,7 +357,11 @@ typedef struct fognet_batch_out {
  *     needed; a failed replication's row is undefined, like its other per-task rows.
  *   The assignment (fognet_replay_assigned_dev's and fognet_run_assigned_dev's assign [R][T])
  *     likewise: 4-B alignment, nothing outside [R][T] read; it is never written, unless the caller
- *     passes the same pointer as out->node, which then holds the same values afterwards. */
+ *     passes the same pointer as out->node, which then holds the same values afterwards.
+ *   The group records (fognet_reduce_groups_dev's out [G], metrics [R][FOGNET_REP_METRICS], defined
+ *     [R], n_ungrouped [1], group_of [R]) likewise: 8-B alignment (defined and group_of: 4 B), nothing
+ *     outside them or stats [R] touched, no initialisation needed; a failed replication's metrics
+ *     row is all INT64_MIN and its defined word 0. */
 
 /* count / min / max / exact signed 128-bit sum and 192-bit sum of squares of a
  * signal's raw emitted values (min_raw = INT64_MAX, max_raw = INT64_MIN when
@@ -1033,6 +1037,84 @@ void fognet_job_stats_merge(fognet_job_stats *acc, const fognet_job_stats *other
  * does per replication; energy is added in call order): for callers of the
  * host-buffer fognet_run_batch. */
 void fognet_job_stats_add_rep(fognet_job_stats *acc, const fognet_rep_stats *rep);
+
+/* Replication groups: the job reduction keyed by the replication's place in the job (a sweep point,
+ * a scenario, a shard) and, per group, the spread of per-replication metrics ACROSS replications --
+ * the method of independent replications: each run's mean, and the mean and standard deviation of
+ * those over the runs.  The pass reads the [R] records alone, so it serves every replay that fills
+ * fognet_rep_stats: materialised, assigned, EXT_HIER and generated (not the v2 model, whose
+ * fognet_v2_stats hold counts only).
+ * Metrics of one replication, exact integers from its record (fognet_rep_metrics); floor is towards
+ * minus infinity (-7 / 2 -> -4):
+ *   0 RESP_MEAN    floor(resp_sum / n_tasks), ticks (resp_sum: unsigned 128 bit)    iff n_tasks > 0
+ *   1 RESP_MAX     resp_max_ticks                                                   iff n_tasks > 0
+ *   2 QUEUE_MEAN   floor(queue_sum / n_qtime), raw (queue_sum: signed 128 bit)      iff n_qtime > 0
+ *   3 QUEUE_MAX    queue_max_raw                                                    iff n_qtime > 0
+ *   4 QUEUED_PPM   floor(n_queued * 10^6 / n_tasks) (signed 128-bit product)        iff n_tasks > 0
+ *   5 MAKESPAN     last_tick                                                        iff last_tick != INT64_MIN
+ *   6 BUSY_S       busy_s                                                           always
+ *   7 MAX_PENDING  max_pending                                                      always
+ *   8 ENERGY_UJ    toInt64(energy_j * 1e6): one IEEE multiply, then floor(x + 0.5) with its own
+ *                  rounding (no fused multiply-add), "Reference signal values"      always
+ * Only a replication with status == FOGNET_OK has metrics (fognet_reduce_stats_dev's rule).  A
+ * defined metric whose value does not fit int64 (a NaN or out-of-range energy: toInt64's
+ * |floor(x + 0.5)| < 2^63; a quotient of inconsistent caller-made records) counts in that metric's
+ * `overflow` and stays out of its moments; an undefined metric adds nothing.
+ * Every field of the group record is an integer updated with integer atomics or merged exactly, so
+ * a record does not depend on the order of its updates: the same call gives the same bytes twice,
+ * and sharding over GPUs changes nothing.  No fp64 sum is kept: the group's energy is
+ * across[FOGNET_METRIC_ENERGY_UJ].sum, in microjoules. */
+#define FOGNET_REP_METRICS 9
+enum {
+    FOGNET_METRIC_RESP_MEAN = 0, FOGNET_METRIC_RESP_MAX, FOGNET_METRIC_QUEUE_MEAN, FOGNET_METRIC_QUEUE_MAX,
+    FOGNET_METRIC_QUEUED_PPM, FOGNET_METRIC_MAKESPAN, FOGNET_METRIC_BUSY_S, FOGNET_METRIC_MAX_PENDING,
+    FOGNET_METRIC_ENERGY_UJ
+};
+typedef struct fognet_group_stats {
+    int64_t n_reps, n_failed, n_ref_aborted;    /* fognet_job_stats' rules, over the group's members */
+    int64_t n_tasks, n_queued, n_started, events;   /* sums over the OK members */
+    fognet_moments queue;   /* pooled over tasks: count = sum of n_qtime, overflow = sum of n_qtime_overflow,
+                               min/max, sum (signed, modulo 2^128) and sq (192 bit) merged from the OK
+                               members' records                                                       */
+    fognet_moments resp;    /* pooled: count = sum of n_tasks, overflow 0                             */
+    fognet_moments across[FOGNET_REP_METRICS];  /* over the group's OK replications, one value each */
+} fognet_group_stats;       /* 848 B, 8-B aligned: 7 words, then 11 fognet_moments */
+
+#define FOGNET_GROUP_LDS_MAX 64   /* groups whose records a workgroup keeps in LDS (64 x 848 B) */
+/* out[g] (device, [G]) = the group record of the replications r with group_of[r] == g (device, [R]
+ * int32; NULL: every replication in group 0).  A replication with group_of[r] outside [0, G) is in
+ * no group and is counted in *n_ungrouped (device, nullable).  A failed replication counts in its
+ * group's n_reps and n_failed, and in n_ref_aborted under fognet_job_stats' rule (status OK or
+ * FOGNET_REF_ABORTED, abort_tick set); it adds nothing else.
+ * metrics (device, [R][FOGNET_REP_METRICS] int64, nullable) and defined (device, [R] uint32,
+ * nullable) take fognet_rep_metrics of every replication, grouped or not: bit m of defined[r] says
+ * that metrics[r][m] is a value the moments take; every other entry (an undefined or overflowed
+ * metric, the whole row of a failed replication) is INT64_MIN with its bit clear.  They are there for
+ * what the moments cannot give, such as quantiles across replications on the host.
+ * Any R; R = 0 gives G empty records (every count and sum 0, min_raw INT64_MAX, max_raw INT64_MIN)
+ * and *n_ungrouped = 0.  G <= 0, a NULL out, or NULL stats with R > 0: FOGNET_ERR_ARG, nothing
+ * written.  The call only enqueues on hip_stream and needs no workspace.  Up to
+ * FOGNET_GROUP_LDS_MAX groups each workgroup accumulates in LDS and adds its non-empty records to
+ * out at its end; above, the accumulators are out itself.  FOGNET_GROUP_STATS=hbm (environment,
+ * testing) forces the latter for every G; the results are identical. */
+int fognet_reduce_groups_dev(fognet_ctx *ctx, const fognet_rep_stats *stats, int32_t R,
+                             const int32_t *group_of, int32_t G, fognet_group_stats *out,
+                             int64_t *metrics, uint32_t *defined, int64_t *n_ungrouped, void *hip_stream);
+/* The metrics of one record (host): value[m] and bit m of *defined for a metric the moments take,
+ * bit m of *overflowed for a defined metric that does not fit int64 (value[m] = INT64_MIN, as for
+ * an undefined one).  The status is not looked at.  defined / overflowed: nullable. */
+void fognet_rep_metrics(const fognet_rep_stats *rep, int64_t value[FOGNET_REP_METRICS], uint32_t *defined,
+                        uint32_t *overflowed);
+/* Host twins, exact: the empty record, one replication added (what the device pass does per
+ * member), and the merge of two records (ranks, shards, groups folded together). */
+void fognet_group_stats_init(fognet_group_stats *s);
+void fognet_group_stats_add_rep(fognet_group_stats *acc, const fognet_rep_stats *rep);
+void fognet_group_stats_merge(fognet_group_stats *acc, const fognet_group_stats *other);
+/* The group as a job record: every integer field equals what fognet_reduce_stats_dev gives for the
+ * group's members alone (last_tick, max_pending and busy_s from across[]; queue_sum's top limb is
+ * the sign of the 128-bit pooled sum and resp_sum's is 0, which is the job's value while the group's
+ * sums stay inside 128 bits, 2^64 tasks of 2^63 ticks); energy_j = (double)(sum of microjoules) * 1e-6. */
+void fognet_group_stats_job(const fognet_group_stats *g, fognet_job_stats *out);
 
 /* Device trace generator: fills arrive/req [R][T] and node params [R][N]
  * (replications r0 .. r0+R-1 of the recipe; r0 lets GPUs shard one job). */

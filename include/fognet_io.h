@@ -126,6 +126,24 @@ int fognet_write_sca_queue(const char *path, const char *run_id, const char *net
 int fognet_write_sca_compare(const char *path, const char *run_id, const char *network, const char *module,
                              const fognet_compare_stats *job, const int64_t *hist, int append);
 
+/* OMNeT++ .sca blocks of replication groups (host; fognet_reduce_groups_dev's records, fognet_hip.h
+ * "Replication groups").  Per group one module -- module[g] (nullable array of G names), else
+ * <network>.replications when G == 1 and <network>.group[g] otherwise -- with the scalars
+ *   replications, "failed replications", "replications the reference aborts"
+ * and one statistic per metric over the group's OK replications (count, mean and stddev are what
+ * an interval needs; no t-quantile table is shipped):
+ *   respMean:replications, respMax:replications       ms (ticks / 10^9)
+ *   queueMean:replications, queueMax:replications     ms (raw * 10^-12)
+ *   queuedShare:replications                          a fraction (ppm / 10^6)
+ *   makespan:replications                             s
+ *   busySeconds:replications, maxPending:replications
+ *   energy:replications                               J
+ * with fognet_write_sca's fields and %.14g formatting, from the exact sums (count 0: -nan).  Each
+ * is followed by the scalar "<metric> replications lost" where its overflow > 0.
+ * append: as fognet_write_sca_nodes. */
+int fognet_write_sca_groups(const char *path, const char *run_id, const char *network, int32_t G,
+                            const fognet_group_stats *groups, const char *const *module, int append);
+
 /* OMNeT++ .sca blocks of per-user records (host; fognet_per_user_stats_dev /
  * fognet_reduce_user_stats_dev, fognet_hip.h): per module
  * <network>.<user_module[u] or "user[u]">.udpApp[0] the statistics `latency:stats`,
