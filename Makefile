@@ -6,7 +6,7 @@ SRC_DIR := fognetsimpp_amd/csrc
 SRCS := $(SRC_DIR)/capi.hip $(SRC_DIR)/replay.hip $(SRC_DIR)/replay_wide.hip $(SRC_DIR)/replay_v2.hip $(SRC_DIR)/replay_region.hip $(SRC_DIR)/decide.hip $(SRC_DIR)/tracegen.hip $(SRC_DIR)/user_stats.hip $(SRC_DIR)/node_stats.hip $(SRC_DIR)/per_user_stats.hip $(SRC_DIR)/signal_vectors.hip $(SRC_DIR)/replay_assigned.hip $(SRC_DIR)/window_stats.hip $(SRC_DIR)/quantiles.hip $(SRC_DIR)/queue_stats.hip $(SRC_DIR)/compare_stats.hip $(SRC_DIR)/group_stats.hip
 HDRS := include/fognet_hip.h include/fognet_io.h $(SRC_DIR)/internal.h $(SRC_DIR)/workspace.h $(SRC_DIR)/replay_common.h $(SRC_DIR)/signals.h $(SRC_DIR)/group_metrics.h
 OBJDIR := build/obj
-OBJS := $(patsubst $(SRC_DIR)/%.hip,$(OBJDIR)/%.o,$(SRCS)) $(OBJDIR)/io.o $(OBJDIR)/group_host.o
+OBJS := $(patsubst $(SRC_DIR)/%.hip,$(OBJDIR)/%.o,$(SRCS)) $(OBJDIR)/io.o $(OBJDIR)/stats_host.o
 HOSTCXX ?= g++
 LIB := fognetsimpp_amd/libfognet_hip.so
 
@@ -27,7 +27,7 @@ $(OBJDIR)/io.o: $(SRC_DIR)/io.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HOSTCXX) -O2 -std=c++17 -fPIC -Wall -ffp-contract=off -Iinclude -c $< -o $@
 
-$(OBJDIR)/group_host.o: $(SRC_DIR)/group_host.cpp $(HDRS)
+$(OBJDIR)/stats_host.o: $(SRC_DIR)/stats_host.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HOSTCXX) -O2 -std=c++17 -fPIC -Wall -ffp-contract=off -Iinclude -c $< -o $@
 
@@ -61,9 +61,9 @@ clean:
 PROF_LIB := build/prof/libfognet_hip.so
 prof: $(SRCS) $(HDRS)
 	@mkdir -p build/prof
-	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -DFOGNET_REPLAY_PROFILE=1 -Iinclude -shared -o $(PROF_LIB) $(SRCS) $(SRC_DIR)/io.cpp $(SRC_DIR)/group_host.cpp
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -DFOGNET_REPLAY_PROFILE=1 -Iinclude -shared -o $(PROF_LIB) $(SRCS) $(SRC_DIR)/io.cpp $(SRC_DIR)/stats_host.cpp
 	@mkdir -p build/prof2
-	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -DFOGNET_REPLAY_PROFILE=2 -Iinclude -shared -o build/prof2/libfognet_hip.so $(SRCS) $(SRC_DIR)/io.cpp $(SRC_DIR)/group_host.cpp
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -DFOGNET_REPLAY_PROFILE=2 -Iinclude -shared -o build/prof2/libfognet_hip.so $(SRCS) $(SRC_DIR)/io.cpp $(SRC_DIR)/stats_host.cpp
 
 .PHONY: prof
 
@@ -93,9 +93,12 @@ asan:
 	$(HOSTCXX) $(ASAN_FLAGS) -std=c++17 -ffp-contract=off -Iinclude -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ \
 	  $(SRC_DIR)/fognet_replay.cpp $(SRC_DIR)/io.cpp -o $(ASAN_DIR)/fognet_replay \
 	  -Lfognetsimpp_amd -lfognet_hip -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$(CURDIR)/fognetsimpp_amd -Wl,-rpath,/opt/rocm/lib
-	$(HOSTCXX) $(ASAN_FLAGS) -std=c++17 -ffp-contract=off -Iinclude tests/c/group_check.cpp $(SRC_DIR)/group_host.cpp \
+	$(HOSTCXX) $(ASAN_FLAGS) -std=c++17 -ffp-contract=off -Iinclude tests/c/group_check.cpp $(SRC_DIR)/stats_host.cpp \
 	  $(SRC_DIR)/io.cpp -o $(ASAN_DIR)/group_check
+	$(HOSTCXX) $(ASAN_FLAGS) -std=c++17 -ffp-contract=off -Iinclude tests/c/stats_check.cpp $(SRC_DIR)/stats_host.cpp \
+	  -o $(ASAN_DIR)/stats_check
 	ASAN_OPTIONS=detect_leaks=1 $(ASAN_DIR)/oracle_check
+	ASAN_OPTIONS=detect_leaks=1 $(ASAN_DIR)/stats_check
 	ASAN_OPTIONS=detect_leaks=1 $(ASAN_DIR)/group_check $(ASAN_DIR)
 	ASAN_OPTIONS=detect_leaks=1 $(ASAN_DIR)/io_check $(ASAN_DIR)
 	ASAN_OPTIONS=detect_leaks=1 $(ASAN_DIR)/io_nodes_check $(ASAN_DIR)
@@ -119,6 +122,6 @@ asan:
 	! ASAN_OPTIONS=detect_leaks=0 $(ASAN_DIR)/fognet_replay -f tests/scenarios/fog5.ini --users 'user[2]' --assign rr \
 	  --policy EXT_LAT --dry-run 2> $(ASAN_DIR)/err.txt
 	grep -q "not together with --policy" $(ASAN_DIR)/err.txt
-	@echo "asan: oracle, io and driver clean"
+	@echo "asan: oracle, io and driver clean; stats_check and group_check clean"
 
 .PHONY: asan

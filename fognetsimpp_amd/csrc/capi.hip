@@ -107,6 +107,22 @@ int set_device(fognet_ctx* c) {
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "hipSetDevice");
 }
 
+// The job reduction of keyed records, recs [R][K] into out [K] (fognet_reduce_{node,queue,window,user}_stats_dev):
+// `negative` and `what` are the entry point's own texts.
+template <class Rec>
+int reduce_keyed(fognet_ctx* c, const Rec* recs, const fognet_rep_stats* stats, int32_t R, int32_t K, Rec* out,
+                 void* stream, hipError_t (*launch)(const Rec*, const fognet_rep_stats*, int32_t, int32_t, Rec*, hipStream_t),
+                 const char* negative, const char* what) {
+  if (!c) return FOGNET_ERR_ARG;
+  if (R < 0 || K < 0) return fail(c, FOGNET_ERR_ARG, negative);
+  if (K == 0) return FOGNET_OK;
+  if (!out || (R > 0 && (!recs || !stats))) return fail(c, FOGNET_ERR_ARG, "null pointer");
+  const int rc = set_device(c);
+  if (rc) return rc;
+  const hipError_t e = launch(recs, stats, R, K, out, (hipStream_t)stream);
+  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, what);
+}
+
 // Validates a batch descriptor; fills the kernel argument block except pointers to outputs.
 // generated: fognet_run_generated_dev (no trace or node-parameter arrays)
 int prepare(fognet_ctx* c, const fognet_batch_in* in, fognet::ReplayArgs* a, bool generated = false) {
@@ -903,14 +919,8 @@ int fognet_node_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet
 
 int fognet_reduce_node_stats_dev(fognet_ctx* c, const fognet_node_stats* node_stats, const fognet_rep_stats* stats,
                                  int32_t R, int32_t N, fognet_node_stats* out, void* stream) {
-  if (!c) return FOGNET_ERR_ARG;
-  if (R < 0 || N < 0) return fail(c, FOGNET_ERR_ARG, "negative R/N");
-  if (N == 0) return FOGNET_OK;
-  if (!out || (R > 0 && (!node_stats || !stats))) return fail(c, FOGNET_ERR_ARG, "null pointer");
-  const int rc = set_device(c);
-  if (rc) return rc;
-  const hipError_t e = fognet::launch_reduce_node_stats(node_stats, stats, R, N, out, (hipStream_t)stream);
-  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "node reduce launch");
+  return reduce_keyed(c, node_stats, stats, R, N, out, stream, fognet::launch_reduce_node_stats, "negative R/N",
+                      "node reduce launch");
 }
 
 // (of `in` only R and T are read: no prepare(), which checks the trace and the policy)
@@ -1154,26 +1164,14 @@ int fognet_queue_stats_dev(fognet_ctx* c, const fognet_batch_in* in, const fogne
 
 int fognet_reduce_queue_stats_dev(fognet_ctx* c, const fognet_queue_stats* qs, const fognet_rep_stats* stats, int32_t R,
                                   int32_t N, fognet_queue_stats* out, void* stream) {
-  if (!c) return FOGNET_ERR_ARG;
-  if (R < 0 || N < 0) return fail(c, FOGNET_ERR_ARG, "negative R/N");
-  if (N == 0) return FOGNET_OK;
-  if (!out || (R > 0 && (!qs || !stats))) return fail(c, FOGNET_ERR_ARG, "null pointer");
-  const int rc = set_device(c);
-  if (rc) return rc;
-  const hipError_t e = fognet::launch_reduce_queue_stats(qs, stats, R, N, out, (hipStream_t)stream);
-  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "queue reduce launch");
+  return reduce_keyed(c, qs, stats, R, N, out, stream, fognet::launch_reduce_queue_stats, "negative R/N",
+                      "queue reduce launch");
 }
 
 int fognet_reduce_window_stats_dev(fognet_ctx* c, const fognet_window_stats* win, const fognet_rep_stats* stats,
                                    int32_t R, int32_t W, fognet_window_stats* out, void* stream) {
-  if (!c) return FOGNET_ERR_ARG;
-  if (R < 0 || W < 0) return fail(c, FOGNET_ERR_ARG, "negative R/W");
-  if (W == 0) return FOGNET_OK;
-  if (!out || (R > 0 && (!win || !stats))) return fail(c, FOGNET_ERR_ARG, "null pointer");
-  const int rc = set_device(c);
-  if (rc) return rc;
-  const hipError_t e = fognet::launch_reduce_window_stats(win, stats, R, W, out, (hipStream_t)stream);
-  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "window reduce launch");
+  return reduce_keyed(c, win, stats, R, W, out, stream, fognet::launch_reduce_window_stats, "negative R/W",
+                      "window reduce launch");
 }
 
 int fognet_signal_vectors_dev(fognet_ctx* c, const fognet_batch_in* in, const fognet_batch_out* out,
@@ -1221,14 +1219,8 @@ int fognet_signal_vectors_dev(fognet_ctx* c, const fognet_batch_in* in, const fo
 
 int fognet_reduce_user_stats_dev(fognet_ctx* c, const fognet_user_stats* user_stats, const fognet_rep_stats* stats,
                                  int32_t R, int32_t U, fognet_user_stats* out, void* stream) {
-  if (!c) return FOGNET_ERR_ARG;
-  if (R < 0 || U < 0) return fail(c, FOGNET_ERR_ARG, "negative R/U");
-  if (U == 0) return FOGNET_OK;
-  if (!out || (R > 0 && (!user_stats || !stats))) return fail(c, FOGNET_ERR_ARG, "null pointer");
-  const int rc = set_device(c);
-  if (rc) return rc;
-  const hipError_t e = fognet::launch_reduce_user_stats(user_stats, stats, R, U, out, (hipStream_t)stream);
-  return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "user reduce launch");
+  return reduce_keyed(c, user_stats, stats, R, U, out, stream, fognet::launch_reduce_user_stats, "negative R/U",
+                      "user reduce launch");
 }
 
 int fognet_run_v2_dev(fognet_ctx* c, const fognet_v2_in* in, fognet_v2_out* out, void* stream) {
@@ -1269,209 +1261,6 @@ int fognet_reduce_stats_dev(fognet_ctx* c, const fognet_rep_stats* stats, int32_
   hipError_t e = fognet::launch_reduce_stats(stats, R, out, static_cast<fognet_job_stats*>(c->red),
                                              (hipStream_t)stream);
   return e == hipSuccess ? FOGNET_OK : hip_fail(c, e, "reduce launch");
-}
-
-void fognet_job_stats_init(fognet_job_stats* s) {
-  if (!s) return;
-  memset(s, 0, sizeof *s);
-  s->queue_min_raw = s->resp_min_ticks = INT64_MAX;
-  s->queue_max_raw = s->resp_max_ticks = s->last_tick = INT64_MIN;
-}
-
-static void add192_host(uint64_t* a, const uint64_t* b) {
-  unsigned __int128 s = (unsigned __int128)a[0] + b[0];
-  a[0] = (uint64_t)s;
-  s = (unsigned __int128)a[1] + b[1] + (uint64_t)(s >> 64);
-  a[1] = (uint64_t)s;
-  a[2] = a[2] + b[2] + (uint64_t)(s >> 64);
-}
-
-void fognet_job_stats_merge(fognet_job_stats* a, const fognet_job_stats* b) {
-  if (!a || !b) return;
-  a->n_reps += b->n_reps;
-  a->n_failed += b->n_failed;
-  a->n_tasks += b->n_tasks;
-  a->n_queued += b->n_queued;
-  a->n_started += b->n_started;
-  a->events += b->events;
-  if (b->last_tick > a->last_tick) a->last_tick = b->last_tick;
-  if (b->queue_min_raw < a->queue_min_raw) a->queue_min_raw = b->queue_min_raw;
-  if (b->queue_max_raw > a->queue_max_raw) a->queue_max_raw = b->queue_max_raw;
-  a->n_qtime += b->n_qtime;
-  a->n_qtime_overflow += b->n_qtime_overflow;
-  a->n_ref_aborted += b->n_ref_aborted;
-  if (b->resp_min_ticks < a->resp_min_ticks) a->resp_min_ticks = b->resp_min_ticks;
-  if (b->resp_max_ticks > a->resp_max_ticks) a->resp_max_ticks = b->resp_max_ticks;
-  if (b->max_pending > a->max_pending) a->max_pending = b->max_pending;
-  a->busy_s += b->busy_s;
-  a->energy_j = a->energy_j + b->energy_j;
-  add192_host(a->queue_sum, b->queue_sum);
-  add192_host(a->queue_sq, b->queue_sq);
-  add192_host(a->resp_sum, b->resp_sum);
-  add192_host(a->resp_sq, b->resp_sq);
-}
-
-void fognet_job_stats_add_rep(fognet_job_stats* a, const fognet_rep_stats* s) {
-  if (!a || !s) return;
-  a->n_reps += 1;
-  /* counted under FOGNET_FLAG_REF_ABORT too (status FOGNET_REF_ABORTED), like reduce_kernel */
-  if ((s->status == FOGNET_OK || s->status == FOGNET_REF_ABORTED) && s->abort_tick != INT64_MAX) a->n_ref_aborted += 1;
-  if (s->status != FOGNET_OK) {
-    a->n_failed += 1;
-    return;
-  }
-  fognet_job_stats b;
-  fognet_job_stats_init(&b);
-  b.n_tasks = s->n_tasks;
-  b.n_queued = s->n_queued;
-  b.n_started = s->n_started;
-  b.events = s->events;
-  b.last_tick = s->last_tick;
-  b.queue_min_raw = s->queue_min_raw;
-  b.queue_max_raw = s->queue_max_raw;
-  b.n_qtime = s->n_qtime;
-  b.n_qtime_overflow = s->n_qtime_overflow;
-  b.resp_min_ticks = s->resp_min_ticks;
-  b.resp_max_ticks = s->resp_max_ticks;
-  b.max_pending = s->max_pending;
-  b.busy_s = s->busy_s;
-  b.energy_j = s->energy_j;
-  b.queue_sum[0] = s->queue_sum_lo;
-  b.queue_sum[1] = s->queue_sum_hi;
-  b.queue_sum[2] = (int64_t)s->queue_sum_hi < 0 ? ~(uint64_t)0 : 0;  // two's complement sign extension
-  b.queue_sq[0] = s->queue_sq_lo;
-  b.queue_sq[1] = s->queue_sq_hi;
-  b.queue_sq[2] = s->queue_sq_top;
-  b.resp_sum[0] = s->resp_sum_lo;
-  b.resp_sum[1] = s->resp_sum_hi;
-  b.resp_sq[0] = s->resp_sq_lo;
-  b.resp_sq[1] = s->resp_sq_hi;
-  fognet_job_stats_merge(a, &b);
-}
-
-static void moments_init_host(fognet_moments* m) {
-  memset(m, 0, sizeof *m);
-  m->min_raw = INT64_MAX;
-  m->max_raw = INT64_MIN;
-}
-
-static void moments_merge_host(fognet_moments* a, const fognet_moments* b) {
-  a->count += b->count;
-  a->overflow += b->overflow;
-  if (b->min_raw < a->min_raw) a->min_raw = b->min_raw;
-  if (b->max_raw > a->max_raw) a->max_raw = b->max_raw;
-  const unsigned __int128 s = (unsigned __int128)a->sum_lo + b->sum_lo;  // two's complement, modulo 2^128
-  a->sum_lo = (uint64_t)s;
-  a->sum_hi = a->sum_hi + b->sum_hi + (uint64_t)(s >> 64);
-  uint64_t q[3] = {a->sq_lo, a->sq_hi, a->sq_top};
-  const uint64_t bq[3] = {b->sq_lo, b->sq_hi, b->sq_top};
-  add192_host(q, bq);
-  a->sq_lo = q[0];
-  a->sq_hi = q[1];
-  a->sq_top = q[2];
-}
-
-void fognet_node_stats_init(fognet_node_stats* s) {
-  if (!s) return;
-  memset(s, 0, sizeof *s);
-  s->last_tick = INT64_MIN;
-  moments_init_host(&s->queue);
-  moments_init_host(&s->resp);
-}
-
-void fognet_node_stats_merge(fognet_node_stats* a, const fognet_node_stats* b) {
-  if (!a || !b) return;
-  a->n_tasks += b->n_tasks;
-  a->n_queued += b->n_queued;
-  a->n_started += b->n_started;
-  a->n_lost += b->n_lost;
-  a->busy_s += b->busy_s;
-  if (b->last_tick > a->last_tick) a->last_tick = b->last_tick;
-  moments_merge_host(&a->queue, &b->queue);
-  moments_merge_host(&a->resp, &b->resp);
-}
-
-void fognet_user_stats_init(fognet_user_stats* s) {
-  if (!s) return;
-  moments_init_host(&s->delay);
-  moments_init_host(&s->latency);
-  moments_init_host(&s->latencyH1);
-  moments_init_host(&s->taskTime);
-}
-
-void fognet_user_stats_merge(fognet_user_stats* a, const fognet_user_stats* b) {
-  if (!a || !b) return;
-  moments_merge_host(&a->delay, &b->delay);
-  moments_merge_host(&a->latency, &b->latency);
-  moments_merge_host(&a->latencyH1, &b->latencyH1);
-  moments_merge_host(&a->taskTime, &b->taskTime);
-}
-
-void fognet_window_stats_init(fognet_window_stats* s) {
-  if (!s) return;
-  memset(s, 0, sizeof *s);
-  moments_init_host(&s->queue);
-  moments_init_host(&s->delay);
-  moments_init_host(&s->latency);
-  moments_init_host(&s->latencyH1);
-  moments_init_host(&s->taskTime);
-}
-
-void fognet_window_stats_merge(fognet_window_stats* a, const fognet_window_stats* b) {
-  if (!a || !b) return;
-  a->n_publish += b->n_publish;
-  a->n_complete += b->n_complete;
-  unsigned __int128 s = (unsigned __int128)a->busy_lo + b->busy_lo;
-  a->busy_lo = (uint64_t)s;
-  a->busy_hi = a->busy_hi + b->busy_hi + (uint64_t)(s >> 64);
-  s = (unsigned __int128)a->insys_lo + b->insys_lo;
-  a->insys_lo = (uint64_t)s;
-  a->insys_hi = a->insys_hi + b->insys_hi + (uint64_t)(s >> 64);
-  moments_merge_host(&a->queue, &b->queue);
-  moments_merge_host(&a->delay, &b->delay);
-  moments_merge_host(&a->latency, &b->latency);
-  moments_merge_host(&a->latencyH1, &b->latencyH1);
-  moments_merge_host(&a->taskTime, &b->taskTime);
-}
-
-void fognet_queue_stats_init(fognet_queue_stats* s) {
-  if (s) memset(s, 0, sizeof *s);
-}
-
-void fognet_queue_stats_merge(fognet_queue_stats* a, const fognet_queue_stats* b) {
-  if (!a || !b) return;
-  auto add128 = [](uint64_t& lo, uint64_t& hi, uint64_t blo, uint64_t bhi) {
-    const unsigned __int128 s = (unsigned __int128)lo + blo;
-    lo = (uint64_t)s;
-    hi = hi + bhi + (uint64_t)(s >> 64);
-  };
-  a->n_enq += b->n_enq;
-  if (b->max_len > a->max_len) a->max_len = b->max_len;
-  add128(a->observed_lo, a->observed_hi, b->observed_lo, b->observed_hi);
-  add128(a->area_lo, a->area_hi, b->area_lo, b->area_hi);
-  for (int q = 0; q < FOGNET_QUEUE_LEVELS_MAX; ++q)
-    add128(a->time_ge[q][0], a->time_ge[q][1], b->time_ge[q][0], b->time_ge[q][1]);
-}
-
-void fognet_compare_stats_init(fognet_compare_stats* s) {
-  if (!s) return;
-  memset(s, 0, sizeof *s);  // (statuses FOGNET_OK)
-  moments_init_host(&s->d_start);
-  moments_init_host(&s->d_service);
-  moments_init_host(&s->d_resp);
-}
-
-void fognet_compare_stats_merge(fognet_compare_stats* a, const fognet_compare_stats* b) {
-  if (!a || !b) return;
-  // the 22 counts from n_reps to rep_worse (a's statuses stay)
-  static_assert(offsetof(fognet_compare_stats, d_start) - offsetof(fognet_compare_stats, n_reps) == 22 * sizeof(int64_t),
-                "the counts are contiguous");
-  int64_t* const aw = &a->n_reps;
-  const int64_t* const bw = &b->n_reps;
-  for (int w = 0; w < 22; ++w) aw[w] = (int64_t)((uint64_t)aw[w] + (uint64_t)bw[w]);
-  moments_merge_host(&a->d_start, &b->d_start);
-  moments_merge_host(&a->d_service, &b->d_service);
-  moments_merge_host(&a->d_resp, &b->d_resp);
 }
 
 int fognet_gen_trace_dev(fognet_ctx* c, const fognet_gen_params* p, int64_t r0, int32_t R, int32_t T, int32_t N,

@@ -1,5 +1,5 @@
 // group_metrics.h — the per-replication metrics of fognet_hip.h "Replication groups", stated once
-// for the device pass (group_stats.hip) and the host twins (capi.hip): nine exact integers formed
+// for the device pass (group_stats.hip) and the host twins (stats_host.cpp): nine exact integers formed
 // from one fognet_rep_stats, each defined or not, each fitting int64 or counted as lost.
 #pragma once
 #include <math.h>
@@ -7,7 +7,7 @@
 
 #include "fognet_hip.h"
 
-// (group_host.cpp is plain host C++: no HIP runtime there)
+// (stats_host.cpp is plain host C++: no HIP runtime there)
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define FOGNET_HD __host__ __device__

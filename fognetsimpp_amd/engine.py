@@ -128,6 +128,45 @@ def _record_buffer(res, nbytes: int, dev, what: str, zero: bool = False, alloc: 
     return (torch.zeros if zero else torch.empty)(nbytes if alloc is None else alloc, dtype=torch.uint8, device=dev)
 
 
+def _reduce_records(ctx, name: str, dtype, recs, what: str, R: int, K=None, stats=None, out=None, stream=None):
+    """Job reduction on the device (``fognet_reduce_<name>_dev``) of ``recs``, the caller's argument ``what``:
+    [R][K] records of ``dtype`` keyed against ``stats`` into [K], or (``stats`` None) [R] records that
+    carry their own statuses into one."""
+    nout = (1 if stats is None else K) * dtype.itemsize
+    dev = (recs if stats is None else stats).device
+    out = _record_buffer(out, nout, dev, "out", alloc=max(nout, 1))
+    if stats is None:
+        args, short = (R,), recs.numel() < R * nout
+    else:
+        args, what = (_ptr(stats), R, K), what + " / stats"
+        short = recs.numel() < R * nout or stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize
+    if short:
+        raise FognetError(_abi.FOGNET_ERR_ARG, f"{what} smaller than R replications")
+    fn = getattr(ctx._lib, f"fognet_reduce_{name}_dev")
+    ctx.check(fn(ctx.handle, _ptr(recs), *args, _ptr(out), _stream_ptr(dev, stream)), f"reduce_{name}")
+    return out[:nout].cpu().numpy().view(dtype)
+
+
+def _merge_records(struct, dtype, init: str, merge: str, records, keyed: bool) -> np.ndarray:
+    """Exact host merge through the C ABI's ``init`` / ``merge`` pair.  ``keyed``: ``records`` are arrays
+    [K] and index k merges over them, into [K]; else every record of ``records`` merges into one."""
+    lib = _abi.load()
+    init, merge = getattr(lib, init), getattr(lib, merge)
+    if keyed:
+        rows = [np.ascontiguousarray(r, dtype=dtype).reshape(-1) for r in records]
+        K = rows[0].size if rows else 0
+    else:
+        rows = np.ascontiguousarray(records, dtype=dtype).reshape(-1, 1)
+        K = 1
+    acc = (struct * K)()
+    for k in range(K):
+        init(C.byref(acc[k]))
+        for row in rows:
+            merge(C.byref(acc[k]), C.byref(struct.from_buffer_copy(row[k].tobytes())))
+    out = np.frombuffer(bytes(acc), dtype=dtype).copy()
+    return out if keyed else out[0]
+
+
 def _to_dev(x, dtype, dev) -> torch.Tensor:
     """A host array or tensor as a contiguous tensor of ``dtype`` on ``dev``."""
     t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
@@ -584,29 +623,14 @@ def reduce_node_stats(ctx: Context, node_stats: torch.Tensor, stats: torch.Tenso
     whose status is OK.  ``node_stats``: :func:`node_stats`'s buffer; ``stats``:
     the replications' records (BatchResult.stats).  Returns NODE_STATS_DTYPE [N];
     ``out``: the device buffer written to (uint8, N * sizeof(fognet_node_stats))."""
-    nout = N * _abi.NODE_STATS_DTYPE.itemsize
-    dev = stats.device
-    out = _record_buffer(out, nout, dev, "out", alloc=max(nout, 1))
-    if node_stats.numel() < R * nout or stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
-        raise FognetError(_abi.FOGNET_ERR_ARG, "node_stats / stats smaller than R replications")
-    ctx.check(ctx._lib.fognet_reduce_node_stats_dev(ctx.handle, _ptr(node_stats), _ptr(stats), R, N, _ptr(out),
-                                                    _stream_ptr(dev)), "reduce_node_stats")
-    return out[:nout].cpu().numpy().view(_abi.NODE_STATS_DTYPE)
+    return _reduce_records(ctx, "node_stats", _abi.NODE_STATS_DTYPE, node_stats, "node_stats", R, N, stats, out)
 
 
 def merge_node_stats(records) -> np.ndarray:
     """Exact host merge of per-node record arrays [N] (e.g. one per GPU after an
     all-gather; fognet_node_stats_merge) into one [N]."""
-    lib = _abi.load()
-    records = [np.ascontiguousarray(r, dtype=_abi.NODE_STATS_DTYPE).reshape(-1) for r in records]
-    N = records[0].size if records else 0
-    acc = (_abi.NodeStats * N)()
-    for j in range(N):
-        lib.fognet_node_stats_init(C.byref(acc[j]))
-        for rec in records:
-            b = _abi.NodeStats.from_buffer_copy(rec[j].tobytes())
-            lib.fognet_node_stats_merge(C.byref(acc[j]), C.byref(b))
-    return np.frombuffer(bytes(acc), dtype=_abi.NODE_STATS_DTYPE).copy()
+    return _merge_records(_abi.NodeStats, _abi.NODE_STATS_DTYPE, "fognet_node_stats_init", "fognet_node_stats_merge",
+                          records, keyed=True)
 
 
 QUEUE_LEVELS = (1, 2, 4, 8, 16, 32, 64, 128)
@@ -649,28 +673,13 @@ def reduce_queue_stats(ctx: Context, queue_stats: torch.Tensor, stats: torch.Ten
     merges node k over the replications whose status is OK (sums, and the maximum of max_len).
     ``queue_stats``: :func:`queue_stats`'s buffer; ``stats``: the replications' records
     (BatchResult.stats).  Returns QUEUE_STATS_DTYPE [N]; ``out``: the device buffer written to."""
-    nout = N * _abi.QUEUE_STATS_DTYPE.itemsize
-    dev = stats.device
-    out = _record_buffer(out, nout, dev, "out", alloc=max(nout, 1))
-    if queue_stats.numel() < R * nout or stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
-        raise FognetError(_abi.FOGNET_ERR_ARG, "queue_stats / stats smaller than R replications")
-    ctx.check(ctx._lib.fognet_reduce_queue_stats_dev(ctx.handle, _ptr(queue_stats), _ptr(stats), R, N, _ptr(out),
-                                                     _stream_ptr(dev)), "reduce_queue_stats")
-    return out[:nout].cpu().numpy().view(_abi.QUEUE_STATS_DTYPE)
+    return _reduce_records(ctx, "queue_stats", _abi.QUEUE_STATS_DTYPE, queue_stats, "queue_stats", R, N, stats, out)
 
 
 def merge_queue_stats(records) -> np.ndarray:
     """Exact host merge of queue record arrays [N] (fognet_queue_stats_merge) into one [N]."""
-    lib = _abi.load()
-    records = [np.ascontiguousarray(r, dtype=_abi.QUEUE_STATS_DTYPE).reshape(-1) for r in records]
-    N = records[0].size if records else 0
-    acc = (_abi.QueueStats * N)()
-    for j in range(N):
-        lib.fognet_queue_stats_init(C.byref(acc[j]))
-        for rec in records:
-            b = _abi.QueueStats.from_buffer_copy(rec[j].tobytes())
-            lib.fognet_queue_stats_merge(C.byref(acc[j]), C.byref(b))
-    return np.frombuffer(bytes(acc), dtype=_abi.QUEUE_STATS_DTYPE).copy()
+    return _merge_records(_abi.QueueStats, _abi.QUEUE_STATS_DTYPE, "fognet_queue_stats_init",
+                          "fognet_queue_stats_merge", records, keyed=True)
 
 
 def compare(ctx: Context, out_a: BatchResult, out_b: BatchResult, res: torch.Tensor | None = None,
@@ -710,26 +719,14 @@ def reduce_compare(ctx: Context, cmp: torch.Tensor, R: int, out: torch.Tensor | 
     """Exact job reduction of comparison records on the device (fognet_reduce_compare_dev): the
     merge of the records whose two statuses are OK.  ``cmp``: :func:`compare`'s buffer.  Returns
     COMPARE_STATS_DTYPE [1]; ``out``: the device buffer written to."""
-    nout = _abi.COMPARE_STATS_DTYPE.itemsize
-    dev = cmp.device
-    out = _record_buffer(out, nout, dev, "out")
-    if cmp.numel() < R * nout:
-        raise FognetError(_abi.FOGNET_ERR_ARG, "cmp smaller than R replications")
-    ctx.check(ctx._lib.fognet_reduce_compare_dev(ctx.handle, _ptr(cmp), R, _ptr(out), _stream_ptr(dev, stream)),
-              "reduce_compare")
-    return out[:nout].cpu().numpy().view(_abi.COMPARE_STATS_DTYPE)
+    return _reduce_records(ctx, "compare", _abi.COMPARE_STATS_DTYPE, cmp, "cmp", R, out=out, stream=stream)
 
 
 def merge_compare(records) -> np.ndarray:
     """Exact host merge of comparison records (fognet_compare_stats_merge) into one, a
     COMPARE_STATS_DTYPE scalar array: counts and moments add, extrema combine, statuses OK."""
-    lib = _abi.load()
-    acc = _abi.CompareStats()
-    lib.fognet_compare_stats_init(C.byref(acc))
-    for rec in np.ascontiguousarray(records, dtype=_abi.COMPARE_STATS_DTYPE).reshape(-1):
-        b = _abi.CompareStats.from_buffer_copy(rec.tobytes())
-        lib.fognet_compare_stats_merge(C.byref(acc), C.byref(b))
-    return np.frombuffer(bytes(acc), dtype=_abi.COMPARE_STATS_DTYPE).copy()[0]
+    return _merge_records(_abi.CompareStats, _abi.COMPARE_STATS_DTYPE, "fognet_compare_stats_init",
+                          "fognet_compare_stats_merge", records, keyed=False)
 
 
 def reduce_groups(ctx: Context, stats: torch.Tensor, R: int, group_of=None, G: int = 1, metrics: bool = False,
@@ -789,13 +786,8 @@ def group_from_reps(reps) -> np.ndarray:
 def merge_group_stats(records) -> np.ndarray:
     """Exact host merge of group records (fognet_group_stats_merge) into one: ranks, shards, or
     groups folded together."""
-    lib = _abi.load()
-    acc = _abi.GroupStats()
-    lib.fognet_group_stats_init(C.byref(acc))
-    for rec in np.ascontiguousarray(records, dtype=_abi.GROUP_STATS_DTYPE).reshape(-1):
-        b = _abi.GroupStats.from_buffer_copy(rec.tobytes())
-        lib.fognet_group_stats_merge(C.byref(acc), C.byref(b))
-    return np.frombuffer(bytes(acc), dtype=_abi.GROUP_STATS_DTYPE).copy()[0]
+    return _merge_records(_abi.GroupStats, _abi.GROUP_STATS_DTYPE, "fognet_group_stats_init",
+                          "fognet_group_stats_merge", records, keyed=False)
 
 
 def group_job(group) -> np.ndarray:
@@ -922,29 +914,14 @@ def reduce_user_stats(ctx: Context, user_stats: torch.Tensor, stats: torch.Tenso
     as a device buffer; ``stats``: the replications' records (BatchResult.stats).
     Returns USER_STATS_DTYPE [U]; ``out``: the device buffer written to (uint8,
     U * sizeof(fognet_user_stats))."""
-    nout = U * _abi.USER_STATS_DTYPE.itemsize
-    dev = stats.device
-    out = _record_buffer(out, nout, dev, "out", alloc=max(nout, 1))
-    if user_stats.numel() < R * nout or stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
-        raise FognetError(_abi.FOGNET_ERR_ARG, "user_stats / stats smaller than R replications")
-    ctx.check(ctx._lib.fognet_reduce_user_stats_dev(ctx.handle, _ptr(user_stats), _ptr(stats), R, U, _ptr(out),
-                                                    _stream_ptr(dev)), "reduce_user_stats")
-    return out[:nout].cpu().numpy().view(_abi.USER_STATS_DTYPE)
+    return _reduce_records(ctx, "user_stats", _abi.USER_STATS_DTYPE, user_stats, "user_stats", R, U, stats, out)
 
 
 def merge_user_stats(records) -> np.ndarray:
     """Exact host merge of user record arrays [U] (e.g. one per GPU after an
     all-gather; fognet_user_stats_merge) into one [U]."""
-    lib = _abi.load()
-    records = [np.ascontiguousarray(r, dtype=_abi.USER_STATS_DTYPE).reshape(-1) for r in records]
-    U = records[0].size if records else 0
-    acc = (_abi.UserStats * U)()
-    for u in range(U):
-        lib.fognet_user_stats_init(C.byref(acc[u]))
-        for rec in records:
-            b = _abi.UserStats.from_buffer_copy(rec[u].tobytes())
-            lib.fognet_user_stats_merge(C.byref(acc[u]), C.byref(b))
-    return np.frombuffer(bytes(acc), dtype=_abi.USER_STATS_DTYPE).copy()
+    return _merge_records(_abi.UserStats, _abi.USER_STATS_DTYPE, "fognet_user_stats_init", "fognet_user_stats_merge",
+                          records, keyed=True)
 
 
 def window_stats(ctx: Context, trace: dict, out: BatchResult, user_of, user_ul, user_dl, t0: int, window: int, W: int,
@@ -991,29 +968,14 @@ def reduce_window_stats(ctx: Context, win: torch.Tensor, stats: torch.Tensor, R:
     :func:`window_stats`'s buffer; ``stats``: the replications' records (BatchResult.stats).
     Returns WINDOW_STATS_DTYPE [W]; ``out``: the device buffer written to (uint8,
     W * sizeof(fognet_window_stats))."""
-    nout = W * _abi.WINDOW_STATS_DTYPE.itemsize
-    dev = stats.device
-    out = _record_buffer(out, nout, dev, "out", alloc=max(nout, 1))
-    if win.numel() < R * nout or stats.numel() < R * _abi.REP_STATS_DTYPE.itemsize:
-        raise FognetError(_abi.FOGNET_ERR_ARG, "win / stats smaller than R replications")
-    ctx.check(ctx._lib.fognet_reduce_window_stats_dev(ctx.handle, _ptr(win), _ptr(stats), R, W, _ptr(out),
-                                                      _stream_ptr(dev)), "reduce_window_stats")
-    return out[:nout].cpu().numpy().view(_abi.WINDOW_STATS_DTYPE)
+    return _reduce_records(ctx, "window_stats", _abi.WINDOW_STATS_DTYPE, win, "win", R, W, stats, out)
 
 
 def merge_window_stats(records) -> np.ndarray:
     """Exact host merge of window record arrays [W] (e.g. one per GPU after an all-gather;
     fognet_window_stats_merge) into one [W]."""
-    lib = _abi.load()
-    records = [np.ascontiguousarray(r, dtype=_abi.WINDOW_STATS_DTYPE).reshape(-1) for r in records]
-    W = records[0].size if records else 0
-    acc = (_abi.WindowStats * W)()
-    for w in range(W):
-        lib.fognet_window_stats_init(C.byref(acc[w]))
-        for rec in records:
-            b = _abi.WindowStats.from_buffer_copy(rec[w].tobytes())
-            lib.fognet_window_stats_merge(C.byref(acc[w]), C.byref(b))
-    return np.frombuffer(bytes(acc), dtype=_abi.WINDOW_STATS_DTYPE).copy()
+    return _merge_records(_abi.WindowStats, _abi.WINDOW_STATS_DTYPE, "fognet_window_stats_init",
+                          "fognet_window_stats_merge", records, keyed=True)
 
 
 def _quantile_args(trace, user_of, user_ul, user_dl, ppm):
@@ -1219,13 +1181,8 @@ def reduce_stats(ctx: Context, stats: torch.Tensor, R: int, out: torch.Tensor | 
 
 def merge_job_stats(records) -> np.ndarray:
     """Exact host merge of job records (e.g. one per GPU after an all-gather)."""
-    lib = _abi.load()
-    acc = _abi.JobStats()
-    lib.fognet_job_stats_init(C.byref(acc))
-    for rec in records:
-        b = _abi.JobStats.from_buffer_copy(np.ascontiguousarray(rec).tobytes())
-        lib.fognet_job_stats_merge(C.byref(acc), C.byref(b))
-    return np.frombuffer(bytes(acc), dtype=_abi.JOB_STATS_DTYPE)[0]
+    return _merge_records(_abi.JobStats, _abi.JOB_STATS_DTYPE, "fognet_job_stats_init", "fognet_job_stats_merge",
+                          records, keyed=False)
 
 
 def job_from_reps(reps) -> np.ndarray:

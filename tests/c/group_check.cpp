@@ -2,7 +2,7 @@
 // (make asan, tests/test_group_stats.py): fognet_rep_metrics' floor rule against the plain 128-bit
 // quotient over the edge cases and seeded random values, the host twins (add_rep, merge, job) against
 // each other on any split of the records, and fognet_write_sca_groups through its paths.
-// Usage: group_check <scratch dir>.  No GPU, no library: linked with group_host.cpp and io.cpp.
+// Usage: group_check <scratch dir>.  No GPU, no library: linked with stats_host.cpp and io.cpp.
 #include <inttypes.h>
 #include <math.h>
 #include <stdio.h>

@@ -2,8 +2,8 @@
 // sanitizer build (`make asan`): a new file and an appended one, a window without an emission,
 // utilisation and tasks in system from sums that need the high limbs, no window at all, and the
 // error paths.  The records come from the host identity and merge of fognet_window_stats, which
-// are checked for their values here but are NOT sanitised: they live in capi.hip and run from
-// the library as it ships; only io.cpp and this file are instrumented.
+// are checked for their values here but are NOT sanitised here: they run from the library as it
+// ships (stats_check.cpp instruments them); only io.cpp and this file are instrumented.
 #include <stdio.h>
 #include <string.h>
 

@@ -255,7 +255,7 @@ def test_group_check_under_sanitizers(tmp_path):
     csrc = os.path.join(ROOT, "fognetsimpp_amd", "csrc")
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c", "group_check.cpp"), os.path.join(csrc, "group_host.cpp"),
+                    os.path.join(ROOT, "tests", "c", "group_check.cpp"), os.path.join(csrc, "stats_host.cpp"),
                     os.path.join(csrc, "io.cpp"), "-o", exe], check=True)
     p = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stdout + p.stderr
